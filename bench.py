@@ -18,7 +18,13 @@ Workloads (BASELINE.json `configs`):
 Weak scaling: every rank owns --envs-per-gpu envs (global env ids rank*N ...), no data-path collective; episode
 returns are all-gathered over RCCL for logging (so101_sim_amd.distributed, outside the timed region).
 
+A plain run sets up, warms up, times exactly --steps steps and prints the headline line.  `--full` also measures and reports
+the rest: five timed windows (`repeats`, `first_window`), per-100-step device clocks (`sustained`), the measured HBM
+copy roofline and PMC figures (`roofline`), per-env diagnostics, event counts, returns and the CPU oracle baseline.
+`--dump-outputs DIR` writes what the last timed step returned (obs, reward, discount, step_type) as float32 .npy files.
+
     python bench.py --gpus 1 --steps 500 --warmup 10
+    python bench.py --gpus 1 --steps 500 --warmup 10 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 bench.py --gpus 8 ...
 """
 import argparse
@@ -37,6 +43,25 @@ VALU_PEAK_TFLOPS = 157.3           # MI355X_MICROARCH.md: fp32 vector peak (256 
 VALU_SUSTAINED_TINST = 0.81        # T wave64 VALU instructions/s the device sustains on plain v_fma_f32 with >= 2 wavefronts per SIMD, measured
                                    # (scripts/microbench/valu_issue.hip, profiles/r06_valu_issue.txt: 103 TFLOP/s; the clock sags to 1.5-2.0 GHz under that load)
 DEFAULT_ENVS = {"handover": 4096, "pickplace": 16384, "mixed": 32768}
+OUTPUT_NAMES = ("obs", "reward", "discount", "step_type")     # what env.step_tensor() returns
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(path: str, outputs) -> None:
+    """`outputs`: the (obs, reward, discount, step_type) tensors of the last timed step, env-major.  Writes them to
+    `path`/<name>.npy as float32.  Above DUMP_BUDGET_BYTES a fixed sample of envs (seed 0) is written instead, and its
+    env indices go to env_index.npy."""
+    import numpy as np
+    arrays = {name: t.detach().cpu().numpy().astype(np.float32) for name, t in zip(OUTPUT_NAMES, outputs)}
+    n = arrays["reward"].shape[0]
+    per_env = sum(a.nbytes for a in arrays.values()) // max(n, 1)
+    if n * per_env > DUMP_BUDGET_BYTES:
+        idx = np.sort(np.random.RandomState(0).choice(n, (DUMP_BUDGET_BYTES - 4096) // (per_env + 8), replace=False))     # (4 KB for the .npy headers)
+        arrays = {name: a[idx] for name, a in arrays.items()}
+        arrays["env_index"] = idx.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def usable_cores() -> int:
@@ -229,26 +254,21 @@ def run_aloha(args, torch, sdist, dev, rank, world, hbm_measured):
     t0 = time.perf_counter()
     reward_sum = torch.zeros((), device=dev)
     for k in range(args.steps):
-        _, r, _, _ = env.step_tensor(tape[args.warmup + k])
-        reward_sum += r.sum()
+        outputs = env.step_tensor(tape[args.warmup + k])
+        if args.full:
+            reward_sum += outputs[1].sum()
     sdist.barrier(); sync()
     elapsed = sdist.max_over_ranks(time.perf_counter() - t0, dev)
-    d = env.diagnostics().cpu().numpy()
-    all_returns = sdist.all_gather_returns(env.episode_returns())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, outputs)
     dist_info = sdist.evidence(1e3 * elapsed / args.steps, dev)      # a collective: every rank calls it
-    plan = env.launch_plan()
+    if args.full:
+        d = env.diagnostics().cpu().numpy()
+        all_returns = sdist.all_gather_returns(env.episode_returns())
+        plan = env.launch_plan()
     if rank == 0:
-        # counters of exactly this build's control step (the launch chain) at 4096 ALOHA envs, when a PMC pass of it is committed (scripts/gpu_pmc_tree.sh)
-        tree_hash = sbuild.source_hash(mpr=args.narrowphase == "mpr")
-        tree_pmc = None
-        pmc_path = os.path.join(ROOT, "profiles", f"pmc_tree_{tree_hash}.json")
-        if not dining and N == 4096 and os.path.exists(pmc_path):
-            with open(pmc_path) as fh:
-                tree_pmc = json.load(fh)
         nq, nv = env.sim.nq, env.sim.nv
-        algo = 4 * (14 + 2 * (nq + nv) + 2 * nv + 74 + 2 * (14 + 16) + 2 + 4) + 1      # action, state r+w, warm start r+w, obs, delay lines r+w, reward / discount, counters, step type
-        achieved = algo * N / (elapsed / args.steps) / 1e9
-        print(json.dumps({
+        out = {
             "metric": "env_steps_per_sec", "value": world * N * args.steps / elapsed, "unit": "env-steps/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "f32", "data": "synthetic",
@@ -260,23 +280,35 @@ def run_aloha(args, torch, sdist, dev, rank, world, hbm_measured):
                        "resets": (f"settled-state store computed before the timed region ({t_store:.1f} s for {2 + (args.warmup + args.steps) // 500} episodes per env)"
                                   if args.settled_store else "placement + settle inside the step calls"),
                        "parallelism": f"env-shard x{world}", "build": sbuild.source_hash(mpr=args.narrowphase == "mpr")},
-            "roofline": {"bound": "latency/valu", "achieved": achieved, "peak": hbm_measured, "unit": "GB/s", "frac": achieved / hbm_measured if hbm_measured else None,
-                         "traffic": (tree_pmc or {}).get("hbm_bytes_per_step"), "peak_spec": HBM_SPEC_GBS, "frac_of_spec": achieved / HBM_SPEC_GBS,
-                         "kernel": f"{plan['path']}: {plan.get('kernels', 'k_tree_step')}; {plan['slices']} env slice(s) on their own streams",
-                         "kernel_ms": 1e3 * elapsed / args.steps, "launches_per_step": plan["kernel_launches"], "memsets_per_step": plan["memsets"],
-                         "compute": None if not tree_pmc else {
-                             "valu_tflops_equiv": tree_pmc["valu_insts_per_step"] * 64 * 2 / (elapsed / args.steps) / 1e12, "peak_tflops": VALU_PEAK_TFLOPS,
-                             "frac": tree_pmc["valu_insts_per_step"] * 64 * 2 / (elapsed / args.steps) / 1e12 / VALU_PEAK_TFLOPS,
-                             "valu_insts_per_env_substep": tree_pmc["valu_insts_per_step"] / (N * 10.0), "active_lane_fraction": tree_pmc.get("active_lane_fraction"),
-                             "wait_fraction": tree_pmc.get("wait_fraction"), "source": f"profiles/pmc_tree_{tree_hash}.json"},
-                         "note": f"algorithmic bytes {algo} B per env-step; the step is bound by its instruction count and the per-CU LDS / L1 traffic of the solver "
-                                 "(DESIGN.md section 8), not by HBM"},
-            "dist": dist_info,
-            "windows": "first window only (the SO100 workloads report the mean of --repeats windows)",
-            "diag_mean": {"contacts": float(d[:, 0].mean()), "constraint_rows": float(d[:, 1].mean()), "solver_iterations": float(d[:, 2].mean()),
-                          "narrowphase_candidates": float(d[:, 3].mean())},
-            "flagged_envs_last_step": int((d[:, 4] != 0).sum()),
-            "mean_reward_per_env_step": float(reward_sum) / (N * args.steps), "mean_episode_return": float(all_returns.mean().item())}))
+            "dist": dist_info}
+        if args.full:
+            # counters of exactly this build's control step (the launch chain) at 4096 ALOHA envs, when a PMC pass of it is committed (scripts/gpu_pmc_tree.sh)
+            tree_hash = sbuild.source_hash(mpr=args.narrowphase == "mpr")
+            tree_pmc = None
+            pmc_path = os.path.join(ROOT, "profiles", f"pmc_tree_{tree_hash}.json")
+            if not dining and N == 4096 and os.path.exists(pmc_path):
+                with open(pmc_path) as fh:
+                    tree_pmc = json.load(fh)
+            algo = 4 * (14 + 2 * (nq + nv) + 2 * nv + 74 + 2 * (14 + 16) + 2 + 4) + 1      # action, state r+w, warm start r+w, obs, delay lines r+w, reward / discount, counters, step type
+            achieved = algo * N / (elapsed / args.steps) / 1e9
+            out.update({
+                "roofline": {"bound": "latency/valu", "achieved": achieved, "peak": hbm_measured, "unit": "GB/s", "frac": achieved / hbm_measured if hbm_measured else None,
+                             "traffic": (tree_pmc or {}).get("hbm_bytes_per_step"), "peak_spec": HBM_SPEC_GBS, "frac_of_spec": achieved / HBM_SPEC_GBS,
+                             "kernel": f"{plan['path']}: {plan.get('kernels', 'k_tree_step')}; {plan['slices']} env slice(s) on their own streams",
+                             "kernel_ms": 1e3 * elapsed / args.steps, "launches_per_step": plan["kernel_launches"], "memsets_per_step": plan["memsets"],
+                             "compute": None if not tree_pmc else {
+                                 "valu_tflops_equiv": tree_pmc["valu_insts_per_step"] * 64 * 2 / (elapsed / args.steps) / 1e12, "peak_tflops": VALU_PEAK_TFLOPS,
+                                 "frac": tree_pmc["valu_insts_per_step"] * 64 * 2 / (elapsed / args.steps) / 1e12 / VALU_PEAK_TFLOPS,
+                                 "valu_insts_per_env_substep": tree_pmc["valu_insts_per_step"] / (N * 10.0), "active_lane_fraction": tree_pmc.get("active_lane_fraction"),
+                                 "wait_fraction": tree_pmc.get("wait_fraction"), "source": f"profiles/pmc_tree_{tree_hash}.json"},
+                             "note": f"algorithmic bytes {algo} B per env-step; the step is bound by its instruction count and the per-CU LDS / L1 traffic of the solver "
+                                     "(DESIGN.md section 8), not by HBM"},
+                "windows": "first window only (the SO100 workloads report the mean of --repeats windows)",
+                "diag_mean": {"contacts": float(d[:, 0].mean()), "constraint_rows": float(d[:, 1].mean()), "solver_iterations": float(d[:, 2].mean()),
+                              "narrowphase_candidates": float(d[:, 3].mean())},
+                "flagged_envs_last_step": int((d[:, 4] != 0).sum()),
+                "mean_reward_per_env_step": float(reward_sum) / (N * args.steps), "mean_episode_return": float(all_returns.mean().item())})
+        print(json.dumps(out))
     env.close()
     sdist.finalize()
 
@@ -301,11 +333,15 @@ def main():
     ap.add_argument("--solver-tolerance", type=float, default=-1.0, help="<0 = model default (1e-8)")
     ap.add_argument("--pool-size", type=int, default=4096, help="pickplace: states in the pre-grasp pool")
     ap.add_argument("--settled-store", action="store_true", help="aloha: precompute the settled reset states of the run's episodes (outside the timed region)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--repeats", type=int, default=5, help="timed windows of --steps steps; `value` is their mean, all are in `repeats`")
+    ap.add_argument("--full", action="store_true", help="also measure and report everything beyond the headline figure (see the module docstring)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write the last timed step's obs / reward / discount / step_type to DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU oracle baseline")
+    ap.add_argument("--repeats", type=int, default=0, help="timed windows of --steps steps; `value` is their mean, all are in `repeats` "
+                                                           "(0 = one window, five with --full)")
     ap.add_argument("--device", choices=("cuda", "cpu"), default="cuda", help="cpu: tests only (gloo, needs --env-factory)")
     ap.add_argument("--env-factory", default="", help="module:callable replacing task_suite.create_task_env (tests)")
     args = ap.parse_args()
+    args.repeats = args.repeats or (5 if args.full else 1)
 
     if args.pipeline >= 2 and "SO101_HIP_LIB" not in os.environ:
         # the experimental step paths (per-env chaining, merged launches) are not in the default library: build libso101_hip_exp.so and load it
@@ -335,9 +371,8 @@ def main():
     assert (not torch.distributed.is_initialized() and world == 1) or torch.distributed.get_world_size() == args.gpus
 
     from so101_sim_amd import build as sbuild
-    # roofline denominator first: a few seconds of streaming copies, which also take the GPU out of its idle power state
-    # before anything is timed (a fresh box otherwise spends the first timed steps ramping its clocks)
-    hbm_measured = measure_hbm_copy(torch, dev, reps=20) if (rank == 0 and on_gpu) else None
+    # --full: roofline denominator first (streaming copies, which also take the GPU out of its idle power state before anything is timed)
+    hbm_measured = measure_hbm_copy(torch, dev, reps=20) if (args.full and rank == 0 and on_gpu) else None
     if args.workload in ("aloha", "dining"):
         return run_aloha(args, torch, sdist, dev, rank, world, hbm_measured)
     N = args.envs_per_gpu or DEFAULT_ENVS[args.workload]
@@ -430,13 +465,14 @@ def main():
     # never reach it; `--steps 500` does five)
     returns_log = sdist.PeriodicReturnsGather(interval=100, device=dev)
     steps_done = [0]
+    outputs = [None] * len(envs)      # what each env's step_tensor() returned in the latest step
 
     def one_step(i, timed, sample=None):
-        # `i` indexes the action tape (warm-up part, then one K-step slice per timed window).  `sample`: read the per-env diagnostics after this step.  The first warm-up
-        # step does it too (result discarded), so that every torch kernel the sampling needs is loaded before the timed
+        # `i` indexes the action tape (warm-up part, then one K-step slice per timed window).  `sample` (--full): read the per-env diagnostics after
+        # this step.  The first warm-up step does it too (result discarded), so that every torch kernel the sampling needs is loaded before the timed
         # region starts - on a fresh box the lazy load of one kernel costs more than a control step.
         if sample is None:
-            sample = timed and (i - args.warmup) % 10 == 0 and i < args.warmup + args.steps
+            sample = args.full and timed and (i - args.warmup) % 10 == 0 and i < args.warmup + args.steps
         for k, env in enumerate(envs):
             with on_stream(streams[k]):
                 if args.workload == "pickplace":
@@ -447,8 +483,8 @@ def main():
                     act[:, 5] = hold[k][:, 5] - 0.3 + noise[k][i][:, 5]
                 else:
                     act = tapes[k][i]
-                env.step_tensor(act)
-                if (timed or sample) and args.workload != "handover":      # (the headline workload never reaches reward 1: no extra launches there)
+                outputs[k] = env.step_tensor(act)
+                if args.full and (timed or sample) and args.workload != "handover":      # (the headline workload never reaches reward 1: no extra launches there)
                     stats[k]["reward_sum"] += env.reward.sum()
                 if sample:
                     d = env.diagnostics().float()
@@ -466,16 +502,17 @@ def main():
             steps_done[0] += 1
 
     for i in range(args.warmup):
-        one_step(i, False, sample=(i == 0))
+        one_step(i, False, sample=args.full and i == 0)
     sync()
-    for st in stats:
-        for k in st:
-            st[k].zero_()
-    samples[0] = 0
-    for env in envs:
-        env.events(clear=True)
-        if hasattr(env, "sim") and hasattr(env.sim, "chain_stats"):
-            env.sim.chain_stats(clear=True)
+    if args.full:
+        for st in stats:
+            for k in st:
+                st[k].zero_()
+        samples[0] = 0
+        for env in envs:
+            env.events(clear=True)
+            if hasattr(env, "sim") and hasattr(env.sim, "chain_stats"):
+                env.sim.chain_stats(clear=True)
 
     drain = [0.0]
 
@@ -513,15 +550,16 @@ def main():
         segs = [max(t[j].ms_until(t[j + 1]) for t in ticks) for j in range(len(ticks[0]) - 1)] if segment else []
         return host, dev_ms, segs, own, joined
 
-    elapsed_local, kernel_ms, segments, own_local, joined_local = timed_window(segment=100 if args.steps >= 500 else 0)
+    elapsed_local, kernel_ms, segments, own_local, joined_local = timed_window(segment=100 if args.full and args.steps >= 500 else 0)
     elapsed = sdist.max_over_ranks(elapsed_local, dev)
     joined = sdist.max_over_ranks(joined_local, dev)
-    events_first = {}
-    for env in envs:
-        for k, v in env.events().items():
-            events_first[k] = events_first.get(k, 0) + v
-    stats_first = {k: sum(float(st[k]) for st in stats) for k in stats[0]}
-    stats_first["samples"] = samples[0]
+    if args.full:
+        events_first = {}
+        for env in envs:
+            for k, v in env.events().items():
+                events_first[k] = events_first.get(k, 0) + v
+        stats_first = {k: sum(float(st[k]) for st in stats) for k in stats[0]}
+        stats_first["samples"] = samples[0]
     # Further windows of the same length for the spread of the measurement.  They run back to back WITHOUT draining the GPU in
     # between (device events on the launch streams at the window boundaries, one synchronize at the end): windows separated by
     # a host synchronisation measure the clock governor, not the kernels - with the GPU idling for a moment every 20 steps the
@@ -542,17 +580,21 @@ def main():
         for r in range(n_more):
             rep_elapsed.append(sdist.max_over_ranks(1e-3 * max(m[r].ms_until(m[r + 1]) for m in marks), dev))
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, [torch.cat(per_env) for per_env in zip(*outputs)])
+
     # what the process group itself reports (backend, world size, which ranks answered) + every rank's own ms per step of the first window
     dist_info = sdist.evidence(1e3 * own_local / args.steps, dev)
     logged = returns_log.latest()
     dist_info["periodic_returns_gather"] = {"interval_steps": returns_log.interval, "collectives": returns_log.count,
                                             "last": None if logged is None else {"timed_step": logged[0], "envs": int(logged[1].numel()), "mean_return": float(logged[1].float().mean())}}
-    # logging-only exchange: episode returns all-gathered over RCCL/xGMI (not in the timed region)
-    returns = torch.cat([env.episode_returns() for env in envs])
-    all_returns = sdist.all_gather_returns(returns)
-    events = events_first
+    if args.full:
+        # logging-only exchange: episode returns all-gathered over RCCL/xGMI (not in the timed region)
+        returns = torch.cat([env.episode_returns() for env in envs])
+        all_returns = sdist.all_gather_returns(returns)
+        events = events_first
+        stats = stats_first
     n_local = sum(e.n_envs for e in envs)
-    stats = stats_first
 
     path = 0 if args.fused else (args.pipeline if args.pipeline >= 0 else 1)
     if rank == 0:
@@ -560,12 +602,8 @@ def main():
         # `value` = the MEAN over all timed windows (each EXACTLY --steps steps; the first one host-clocked between barrier +
         # synchronize, the others back to back behind it, cut with device events), not the first - and usually best - window alone
         rep_values = [world * n_local * args.steps / e for e in rep_elapsed]
-        first_window = rep_values[0]
         elapsed_mean = sum(rep_elapsed) / len(rep_elapsed)
         value = world * n_local * args.steps / elapsed_mean
-        achieved = ALGO_BYTES_PER_ENV_STEP * n_local / (kernel_ms * 1e-3) / 1e9
-        pmc = load_pmc(build_hash) if args.workload == "handover" and N == 4096 and path == 1 else None
-        env_steps = n_local * args.steps
         names = {"handover": "SO100HandOverBanana, uniform random actions, 500-step episodes with the reference reset (placement + settle, prefetched)",
                  "pickplace": f"SO100HandOverBanana pick-and-place, episodes from a scripted pre-grasp pool of {args.pool_size} states, hold pose + N(0,0.05) actions with the jaw closing",
                  "mixed": "SO100HandOverBanana + SO100HandOverPen halves on two streams, uniform random actions, per-env prop mass scale U(0.5,1.5)"}
@@ -574,9 +612,6 @@ def main():
             "metric": "env_steps_per_sec", "value": value, "unit": "env-steps/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * elapsed_mean / args.steps,
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "first_window": {"value": first_window, "ms_per_step": 1e3 * elapsed / args.steps,
-                             "closing_sync": "device-wide synchronize" if drain[0] <= 0.01 * joined else
-                                             f"launch streams joined; the device-wide synchronize returned {drain[0]:.2f} s later (background reset prefetch of future episodes)"},
             "dist": dist_info,
             "config": {"workload": f"{names[args.workload]}; {n_local} lock-step envs per GPU, proprioceptive obs"
                                    + (f" (BASELINE.json configs[{cfg_index}]" + (" per-GPU share)" if cfg_index == 4 else ")") if cfg_index else ""),
@@ -585,69 +620,78 @@ def main():
                        "solver_iterations": args.solver_iterations or 100,
                        "solver_tolerance": args.solver_tolerance if args.solver_tolerance >= 0 else 1e-8,
                        "parallelism": f"env-shard x{world}", "build": build_hash},
-            "roofline": {"bound": "latency/valu", "achieved": achieved, "peak": hbm_measured, "unit": "GB/s",
-                         "frac": achieved / hbm_measured if hbm_measured else None, "traffic": (pmc or {}).get("hbm_bytes_per_step"),
-                         "peak_spec": HBM_SPEC_GBS, "frac_of_spec": achieved / HBM_SPEC_GBS,
-                         "kernel": {0: "k_step", 1: f"k_order + {args.groups or 4} env slices x (k_pipe_begin + substeps x (k_narrow + k_pipe_solve))",
-                                    2: "k_order + k_pipe_begin + k_chain (persistent: narrowphase chunks and per-env solve items from device-side queues)",
-                                    3: f"k_order + {args.groups or 4} env slices x (k_pipe_begin + (1 + substeps) x k_pipe_merged: solve of substep s, then narrowphase chunks of s + 1)"}[path],
-                         "kernel_ms": kernel_ms, "launches_per_step": {0: 1, 1: 1 + (args.groups or 4) * 21, 2: 3, 3: 1 + (args.groups or 4) * 12}[path],
-                         "compute": None if not pmc else {
-                             "valu_tflops_equiv": pmc.get("valu_insts_per_step", 0) * 64 * 2 / (kernel_ms * 1e-3) / 1e12,
-                             "peak_tflops": VALU_PEAK_TFLOPS,
-                             "frac": pmc.get("valu_insts_per_step", 0) * 64 * 2 / (kernel_ms * 1e-3) / 1e12 / VALU_PEAK_TFLOPS,
-                             "frac_of_measured_issue_rate": pmc.get("valu_insts_per_step", 0) / (kernel_ms * 1e-3) / 1e12 / VALU_SUSTAINED_TINST,
-                             "active_lane_fraction": pmc.get("active_lane_fraction"),
-                             "wait_fraction": pmc.get("wait_fraction"), "source": f"profiles/pmc_{build_hash}.json"},
-                         "note": "HBM fraction as the metric asks: algorithmic bytes (620 B/env-step x envs) / device time of the step's launch "
-                                 "chain / MEASURED device-to-device copy bandwidth of this GPU; the path is bound by dependent-issue latency of "
-                                 "wave-level geometry / solver code, not by HBM (DESIGN.md section 7); `compute` = VALU wave-instructions x 64 lanes "
-                                 "x 2 flop over the same time against the fp32 vector peak, from the PMC pass of this exact build when one is committed"},
-            "diag_mean": {k2: float(stats[k]) / max(stats["samples"], 1) for k, k2 in (("ncon", "contacts"), ("nefc", "constraint_rows"), ("iters", "solver_iterations"), ("ncand", "narrowphase_candidates"))},
-            "events_per_env_step": {k: v / env_steps for k, v in events.items()},
-            "events": events,
-            "mean_reward_per_env_step": float(stats["reward_sum"]) / env_steps,
-            "mean_episode_return": float(all_returns.mean().item()),
         }
-        import statistics
-        out["repeats"] = {"n": len(rep_values), "values": rep_values, "mean": statistics.fmean(rep_values),
-                          "std": statistics.pstdev(rep_values) if len(rep_values) > 1 else 0.0,
-                          "note": "`value` is the mean over these windows (total steps / total time).  The first window is the --steps steps "
-                                  "that follow the warm-up, bracketed by barrier + synchronize on both sides (host clock; `first_window`).  "
-                                  "The others are further windows of the same length run back to back behind it, timed with device events "
-                                  "at the window boundaries (max over launch streams and ranks) and one synchronize at the end"}
-        if segments:
-            seg_rates = [n_local * 100 / (ms * 1e-3) for ms in segments]
-            out["sustained"] = {"steps": args.steps, "env_steps_per_s": value,
-                                "host_env_steps_per_s": n_local * world * args.steps / joined,
-                                "device_env_steps_per_s": n_local * world * args.steps / (1e-3 * sum(segments)),
-                                "device_wide_sync_env_steps_per_s": n_local * world * args.steps / (joined + drain[0]),
-                                "prefetch_drain_s": drain[0],
-                                "per_100_steps_env_steps_per_s": seg_rates,
-                                "min": min(seg_rates), "max": max(seg_rates),
-                                "note": "one window long enough for every env to pass its time limit (auto-reset inside); device time "
-                                        "of each 100-step slice on rank 0, the way the reference logs its step time (run_eval.py:103-124). "
-                                        "`host_env_steps_per_s` = host clock from the barrier to the moment the launch streams are "
-                                        "joined (stream.synchronize(): the K steps are complete - what a caller that synchronises its own "
-                                        "stream measures, max over ranks) = `env_steps_per_s` = `value`; the contract's device-wide "
-                                        "synchronize is issued right behind it and returned `prefetch_drain_s` later "
-                                        "(`device_wide_sync_env_steps_per_s`): it also waits for the reset prefetch of FUTURE "
-                                        "episodes that the last mass reset started on the library's low-priority stream (in a longer run that "
-                                        "work overlaps the next episode's steps - the dips of `per_100_steps` - instead of standing alone at the "
-                                        "end; when the wait is below 1 % of the window, as in the driver's 20-step windows, `value` is clocked at "
-                                        "the device-wide synchronize itself); `device_env_steps_per_s` = the same steps over the device time of the launch streams"}
         if hasattr(envs[0], "sim") and hasattr(envs[0].sim, "info"):
             out["config"]["step_path"] = envs[0].sim.info()
+        if args.full:
+            achieved = ALGO_BYTES_PER_ENV_STEP * n_local / (kernel_ms * 1e-3) / 1e9
+            pmc = load_pmc(build_hash) if args.workload == "handover" and N == 4096 and path == 1 else None
+            env_steps = n_local * args.steps
+            out.update({
+                "first_window": {"value": rep_values[0], "ms_per_step": 1e3 * elapsed / args.steps,
+                                 "closing_sync": "device-wide synchronize" if drain[0] <= 0.01 * joined else
+                                                 f"launch streams joined; the device-wide synchronize returned {drain[0]:.2f} s later (background reset prefetch of future episodes)"},
+                "roofline": {"bound": "latency/valu", "achieved": achieved, "peak": hbm_measured, "unit": "GB/s",
+                             "frac": achieved / hbm_measured if hbm_measured else None, "traffic": (pmc or {}).get("hbm_bytes_per_step"),
+                             "peak_spec": HBM_SPEC_GBS, "frac_of_spec": achieved / HBM_SPEC_GBS,
+                             "kernel": {0: "k_step", 1: f"k_order + {args.groups or 4} env slices x (k_pipe_begin + substeps x (k_narrow + k_pipe_solve))",
+                                        2: "k_order + k_pipe_begin + k_chain (persistent: narrowphase chunks and per-env solve items from device-side queues)",
+                                        3: f"k_order + {args.groups or 4} env slices x (k_pipe_begin + (1 + substeps) x k_pipe_merged: solve of substep s, then narrowphase chunks of s + 1)"}[path],
+                             "kernel_ms": kernel_ms, "launches_per_step": {0: 1, 1: 1 + (args.groups or 4) * 21, 2: 3, 3: 1 + (args.groups or 4) * 12}[path],
+                             "compute": None if not pmc else {
+                                 "valu_tflops_equiv": pmc.get("valu_insts_per_step", 0) * 64 * 2 / (kernel_ms * 1e-3) / 1e12,
+                                 "peak_tflops": VALU_PEAK_TFLOPS,
+                                 "frac": pmc.get("valu_insts_per_step", 0) * 64 * 2 / (kernel_ms * 1e-3) / 1e12 / VALU_PEAK_TFLOPS,
+                                 "frac_of_measured_issue_rate": pmc.get("valu_insts_per_step", 0) / (kernel_ms * 1e-3) / 1e12 / VALU_SUSTAINED_TINST,
+                                 "active_lane_fraction": pmc.get("active_lane_fraction"),
+                                 "wait_fraction": pmc.get("wait_fraction"), "source": f"profiles/pmc_{build_hash}.json"},
+                             "note": "HBM fraction as the metric asks: algorithmic bytes (620 B/env-step x envs) / device time of the step's launch "
+                                     "chain / MEASURED device-to-device copy bandwidth of this GPU; the path is bound by dependent-issue latency of "
+                                     "wave-level geometry / solver code, not by HBM (DESIGN.md section 7); `compute` = VALU wave-instructions x 64 lanes "
+                                     "x 2 flop over the same time against the fp32 vector peak, from the PMC pass of this exact build when one is committed"},
+                "diag_mean": {k2: float(stats[k]) / max(stats["samples"], 1) for k, k2 in (("ncon", "contacts"), ("nefc", "constraint_rows"), ("iters", "solver_iterations"), ("ncand", "narrowphase_candidates"))},
+                "events_per_env_step": {k: v / env_steps for k, v in events.items()},
+                "events": events,
+                "mean_reward_per_env_step": float(stats["reward_sum"]) / env_steps,
+                "mean_episode_return": float(all_returns.mean().item()),
+            })
+            import statistics
+            out["repeats"] = {"n": len(rep_values), "values": rep_values, "mean": statistics.fmean(rep_values),
+                              "std": statistics.pstdev(rep_values) if len(rep_values) > 1 else 0.0,
+                              "note": "`value` is the mean over these windows (total steps / total time).  The first window is the --steps steps "
+                                      "that follow the warm-up, bracketed by barrier + synchronize on both sides (host clock; `first_window`).  "
+                                      "The others are further windows of the same length run back to back behind it, timed with device events "
+                                      "at the window boundaries (max over launch streams and ranks) and one synchronize at the end"}
+            if segments:
+                seg_rates = [n_local * 100 / (ms * 1e-3) for ms in segments]
+                out["sustained"] = {"steps": args.steps, "env_steps_per_s": value,
+                                    "host_env_steps_per_s": n_local * world * args.steps / joined,
+                                    "device_env_steps_per_s": n_local * world * args.steps / (1e-3 * sum(segments)),
+                                    "device_wide_sync_env_steps_per_s": n_local * world * args.steps / (joined + drain[0]),
+                                    "prefetch_drain_s": drain[0],
+                                    "per_100_steps_env_steps_per_s": seg_rates,
+                                    "min": min(seg_rates), "max": max(seg_rates),
+                                    "note": "one window long enough for every env to pass its time limit (auto-reset inside); device time "
+                                            "of each 100-step slice on rank 0, the way the reference logs its step time (run_eval.py:103-124). "
+                                            "`host_env_steps_per_s` = host clock from the barrier to the moment the launch streams are "
+                                            "joined (stream.synchronize(): the K steps are complete - what a caller that synchronises its own "
+                                            "stream measures, max over ranks) = `env_steps_per_s` = `value`; the contract's device-wide "
+                                            "synchronize is issued right behind it and returned `prefetch_drain_s` later "
+                                            "(`device_wide_sync_env_steps_per_s`): it also waits for the reset prefetch of FUTURE "
+                                            "episodes that the last mass reset started on the library's low-priority stream (in a longer run that "
+                                            "work overlaps the next episode's steps - the dips of `per_100_steps` - instead of standing alone at the "
+                                            "end; when the wait is below 1 % of the window, as in the driver's 20-step windows, `value` is clocked at "
+                                            "the device-wide synchronize itself); `device_env_steps_per_s` = the same steps over the device time of the launch streams"}
             if path == 2:
                 out["config"]["chain_stats"] = envs[0].sim.chain_stats()
-        if not args.no_cpu_baseline and on_gpu:
-            # world > 1 as well: rank 0 alone, after the timed region and after every collective of the run - the other
-            # ranks are not held at a barrier for it, they finalize and exit while rank 0 times the oracle on the host cores
-            if world > 1:
-                sdist.finalize()
-            out["cpu_baseline"] = cpu_baseline()
-            if world > 1:
-                out["cpu_baseline"]["note_ranks"] = f"timed on rank 0 of {world} after the GPU windows, the other ranks idle or gone"
+            if not args.no_cpu_baseline and on_gpu:
+                # world > 1 as well: rank 0 alone, after the timed region and after every collective of the run - the other
+                # ranks are not held at a barrier for it, they finalize and exit while rank 0 times the oracle on the host cores
+                if world > 1:
+                    sdist.finalize()
+                out["cpu_baseline"] = cpu_baseline()
+                if world > 1:
+                    out["cpu_baseline"]["note_ranks"] = f"timed on rank 0 of {world} after the GPU windows, the other ranks idle or gone"
         print(json.dumps(out))
     sdist.finalize()
 

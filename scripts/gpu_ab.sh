@@ -8,7 +8,7 @@ out=$O/${TAG}_ab.txt; : > $out
 run() {  # name libpath extra-args
   local n=$1 lib=$2; shift; shift
   for rep in 1 2; do
-    if [ -n "$lib" ]; then SO101_HIP_LIB=$lib python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline "$@" > /tmp/ab_$n.json 2>/tmp/ab_$n.err; else python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline "$@" > /tmp/ab_$n.json 2>/tmp/ab_$n.err; fi
+    if [ -n "$lib" ]; then SO101_HIP_LIB=$lib python3 bench.py --steps 20 --warmup 5 --full --no-cpu-baseline "$@" > /tmp/ab_$n.json 2>/tmp/ab_$n.err; else python3 bench.py --steps 20 --warmup 5 --full --no-cpu-baseline "$@" > /tmp/ab_$n.json 2>/tmp/ab_$n.err; fi
     python3 - "$n" /tmp/ab_$n.json "$@" >> $out <<'PY'
 import json, sys
 n, f = sys.argv[1], sys.argv[2]

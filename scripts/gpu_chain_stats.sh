@@ -2,7 +2,7 @@
 # chained step: throughput + where the persistent wavefronts' time goes.  Usage: gpu_chain_stats.sh TAG [bench args]
 R=${GRAFT_REPO_ROOT:-/root/repo}; O=$R/gpurun_out; mkdir -p $O
 cd $R; T=$1; shift
-timeout 300 python bench.py --pipeline 2 --steps 20 --warmup 5 --no-cpu-baseline --repeats 3 "$@" > $O/${T}_bench.json 2> $O/${T}_bench.err || tail -20 $O/${T}_bench.err
+timeout 300 python bench.py --pipeline 2 --steps 20 --warmup 5 --full --no-cpu-baseline --repeats 3 "$@" > $O/${T}_bench.json 2> $O/${T}_bench.err || tail -20 $O/${T}_bench.err
 python3 - <<PY
 import json
 d = json.loads(open("$O/${T}_bench.json").read().strip().splitlines()[-1])

@@ -39,6 +39,6 @@ print("mean narrowphase candidates / contacts per env at steps 10, 60, 120:  wit
 for off in (0, 1, 0, 1):
     env = dict(os.environ); env.pop(VAR, None)
     if off: env[VAR] = "1"
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5", "--no-cpu-baseline"], env=env, capture_output=True, text=True)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5", "--full", "--no-cpu-baseline"], env=env, capture_output=True, text=True)
     d = json.loads(r.stdout.strip().splitlines()[-1])
     print(VAR + " %-3s  %8.1f k env-steps/s  windows %s  candidates per env %.2f" % ("set" if off else "-", d["value"] / 1e3, [round(v / 1e3) for v in d["repeats"]["values"]], d["diag_mean"]["narrowphase_candidates"]))

@@ -24,6 +24,7 @@ class StubEnv:
         self.ids = torch.arange(env_id_base, env_id_base + n_envs, dtype=torch.float32)
         self.ret = torch.zeros(n_envs)
         self.reward = torch.zeros(n_envs)
+        self.discount = torch.ones(n_envs)
         self.obs = torch.zeros(n_envs, 18)
         self.step_type = torch.ones(n_envs, dtype=torch.uint8)
         self.delay = 0.01 * (1 + 2 * int(os.environ.get("RANK", "0")))
@@ -38,6 +39,9 @@ class StubEnv:
         assert act.shape == (self.n_envs, 6)
         time.sleep(self.delay)
         self.ret += self.ids          # a function of the GLOBAL env id, like the kernels' RNG keying
+        self.reward.copy_(self.ret)   # (an output that counts the steps taken)
+        self.obs[:, 12:18] = act      # the commanded joints, as in the real observation
+        return self.obs, self.reward, self.discount, self.step_type
 
     def diagnostics(self):
         return torch.zeros(self.n_envs, 8, dtype=torch.int32)

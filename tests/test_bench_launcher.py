@@ -5,6 +5,8 @@ import os
 import subprocess
 import sys
 
+import numpy as np
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -17,7 +19,7 @@ def _run(extra, env_extra=None, timeout=300):
 
 
 def test_gpus_2_spawns_two_ranks_and_reports_the_whole_job():
-    r = _run(["--gpus", "2", "--steps", "4", "--warmup", "1", "--envs-per-gpu", "8", "--repeats", "2"])
+    r = _run(["--gpus", "2", "--steps", "4", "--warmup", "1", "--envs-per-gpu", "8", "--repeats", "2", "--full"])
     assert r.returncode == 0, r.stderr[-2000:]
     line = [x for x in r.stdout.splitlines() if x.startswith("{")]
     assert len(line) == 1, r.stdout
@@ -57,7 +59,7 @@ def test_world_size_mismatch_is_refused():
 
 
 def test_single_rank_line_has_the_contract_keys():
-    r = _run(["--steps", "3", "--warmup", "1", "--envs-per-gpu", "4", "--repeats", "1"])
+    r = _run(["--steps", "3", "--warmup", "1", "--envs-per-gpu", "4", "--repeats", "1", "--full"])
     assert r.returncode == 0, r.stderr[-2000:]
     out = json.loads([x for x in r.stdout.splitlines() if x.startswith("{")][0])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
@@ -71,7 +73,7 @@ def test_single_rank_line_has_the_contract_keys():
 def test_tree_workload_with_two_ranks_prints_its_line():
     """`bench.py --workload aloha --gpus 2` (the process-group evidence is a collective and was called by rank 0 only - rank 0 then hung):
     the real run_aloha with two gloo ranks and a stub env; one line, both ranks in `dist`, the whole-job value from the slower rank's time."""
-    r = _run(["--workload", "aloha", "--gpus", "2", "--steps", "3", "--warmup", "1", "--envs-per-gpu", "8"], timeout=180)
+    r = _run(["--workload", "aloha", "--gpus", "2", "--steps", "3", "--warmup", "1", "--envs-per-gpu", "8", "--full"], timeout=180)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [x for x in r.stdout.splitlines() if x.startswith("{")]
     assert len(line) == 1, r.stdout
@@ -81,3 +83,35 @@ def test_tree_workload_with_two_ranks_prints_its_line():
     assert d["backend"] == "gloo" and d["world_size"] == 2 and d["ranks"] == [0, 1] and len(d["per_rank"]) == 2
     assert abs(out["value"] - 16 * 3 / (out["ms_per_step"] * 3e-3)) < 1e-6 * out["value"]
     assert abs(out["mean_episode_return"] - 4 * 7.5) < 1e-4
+
+
+def _line(r):
+    assert r.returncode == 0, r.stderr[-2000:]
+    return json.loads([x for x in r.stdout.splitlines() if x.startswith("{")][0])
+
+
+def test_plain_run_times_exactly_the_given_steps_and_dumps_the_last_outputs(tmp_path):
+    """A plain run is the headline alone: --steps timed steps after the warm-up, one line without the figures of --full, and with
+    --dump-outputs the four outputs of the last step as float32 .npy files, the same on every run."""
+    dumps = []
+    for k in range(2):
+        out = _line(_run(["--steps", "3", "--warmup", "2", "--envs-per-gpu", "4", "--dump-outputs", str(tmp_path / f"run{k}")]))
+        assert out["metric"] == "env_steps_per_sec" and out["unit"] == "env-steps/s" and out["higher_is_better"] is True and out["dtype"] == "f32"
+        assert out["steps"] == 3 and abs(out["value"] - 4 * 3 / (out["ms_per_step"] * 3e-3)) < 1e-6 * out["value"]
+        assert out["ms_per_step"] >= 10.0 * 0.9          # the stub sleeps 10 ms per step on rank 0
+        for key in ("roofline", "repeats", "first_window", "cpu_baseline", "diag_mean", "events", "mean_episode_return"):
+            assert key not in out
+        dumps.append({n: np.load(tmp_path / f"run{k}" / f"{n}.npy") for n in ("obs", "reward", "discount", "step_type")})
+    a, b = dumps
+    assert all(x.dtype == np.float32 for x in a.values())
+    assert a["obs"].shape == (4, 18) and a["reward"].shape == a["discount"].shape == a["step_type"].shape == (4,)
+    # the stub's reward counts the steps taken: 2 warm-up + 3 timed steps of env ids 0..3, and nothing after them
+    np.testing.assert_array_equal(a["reward"], 5 * np.arange(4, dtype=np.float32))
+    for n in a:
+        np.testing.assert_array_equal(a[n], b[n])
+
+
+def test_tree_workload_plain_run_dumps_its_outputs(tmp_path):
+    out = _line(_run(["--workload", "aloha", "--steps", "2", "--warmup", "1", "--envs-per-gpu", "4", "--dump-outputs", str(tmp_path)]))
+    assert out["steps"] == 2 and "roofline" not in out and "mean_episode_return" not in out
+    assert np.load(tmp_path / "obs.npy").shape == (4, 18) and np.load(tmp_path / "discount.npy").dtype == np.float32
