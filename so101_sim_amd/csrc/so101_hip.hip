@@ -4,6 +4,7 @@
 #include "so101_blob.hpp"
 #include "../../include/so101.h"
 #include "so101_launch.hpp"
+#include "so101_tables.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -169,8 +170,10 @@ int build_model(so101_sim* s, const BlobView& b) {
     if (!in_range("arm_body", nbody, false) || !in_range("free_body", nbody, false) || !in_range("body_parent", nbody, false) ||
         !in_range("geom_body", nbody, false) || !in_range("pair_geom", ngeom, false) || !in_range("task_object_body", nbody, false) ||
         !in_range("task_container_body", nbody, false)) return fail("blob index array out of range");
-    auto gva = b.I("geom_vertadr"), gvn = b.I("geom_vertnum");
+    auto gva = b.I("geom_vertadr"), gvn = b.I("geom_vertnum"), gty = b.I("geom_type");
     for (size_t g = 0; g < ngeom; g++) if (gvn[g] > 0 && (gva[g] < 0 || (size_t)gva[g] + (size_t)gvn[g] > nvert)) return fail("geom vertex range outside mesh_vert");
+    // (the support tables and every support query of a hull need at least one vertex)
+    for (size_t g = 0; g < ngeom; g++) if (gty[g] == G_MESH && gvn[g] <= 0) return fail("mesh geom without vertices (geom_vertnum <= 0)");
   }
   DevModel& M = s->hm;
   int nq = b.I("nq")[0], nv = b.I("nv")[0], nu = b.I("nu")[0], nbody = b.I("nbody")[0], ngeom = b.I("ngeom")[0];
@@ -288,68 +291,17 @@ int build_model(so101_sim* s, const BlobView& b) {
     if (gtype[g1] > gtype[g2]) std::swap(g1, g2);
     packed[k] = (unsigned int)g1 | ((unsigned int)g2 << 8) | ((gtype[g1] == G_PLANE ? 1u : 0u) << 16);
   }
-  // support-bound tables of the hulls (so101_model.hpp DevModel::hull_sbt, obb_filter): in double, rounded up to float
+  // support-bound tables of the hulls (so101_model.hpp DevModel::hull_sbt, obb_filter; so101_tables.hpp)
   std::vector<float> sbt((size_t)ngeom * SBT_DIM, 0.f);
-  for (int g = 0; g < ngeom; g++) {
-    if (gtype[g] != G_MESH) continue;
-    for (int face = 0; face < 6; face++) {
-      int ax = face / 2; double sg = (face & 1) ? -1.0 : 1.0;
-      for (int iu = 0; iu < SBT_GRID; iu++)
-        for (int iv = 0; iv < SBT_GRID; iv++) {
-          const double step = 2.0 / (SBT_GRID - 1);
-          double c[3]; c[ax] = sg; c[(ax + 1) % 3] = -1.0 + step * iu; c[(ax + 2) % 3] = -1.0 + step * iv;
-          double best = -1e300;
-          for (int k = gva[g]; k < gva[g] + gvn[g]; k++) best = std::max(best, (double)mv[3 * k] * c[0] + (double)mv[3 * k + 1] * c[1] + (double)mv[3 * k + 2] * c[2]);
-          float f = (float)best;
-          if ((double)f < best) f = std::nextafterf(f, 3.0e38f);
-          sbt[(size_t)g * SBT_DIM + (face * SBT_GRID + iu) * SBT_GRID + iv] = f;
-        }
-    }
-  }
+  for (int g = 0; g < ngeom; g++)
+    if (gtype[g] == G_MESH) build_support_bounds(&mv[3 * (size_t)gva[g]], gvn[g], &sbt[(size_t)g * SBT_DIM]);
   // support-vertex lists (so101_model.hpp DevModel::hl_entry): per hull and cube-map cell the vertices that can win a support query there
   std::vector<float> hle; std::vector<unsigned int> hlo((size_t)ngeom * (HL_CELLS + 1), 0u);
   const bool hl_off_env = getenv("SO101_NO_HL") != nullptr;          // (tests and kernel experiments: every query scans the whole hull, as until round 6)
   for (int g = 0; g < ngeom; g++) {
     unsigned int* off = &hlo[(size_t)g * (HL_CELLS + 1)];
     if (gtype[g] != G_MESH || hl_off_env) { for (int c = 0; c <= HL_CELLS; c++) off[c] = (unsigned int)(hle.size() / 4); continue; }
-    const int n = gvn[g]; const float* V = &mv[3 * (size_t)gva[g]];
-    double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
-    for (int k = 0; k < n; k++) for (int a = 0; a < 3; a++) { lo[a] = std::min(lo[a], (double)V[3 * k + a]); hi[a] = std::max(hi[a], (double)V[3 * k + a]); }
-    const double diam = std::sqrt((hi[0] - lo[0]) * (hi[0] - lo[0]) + (hi[1] - lo[1]) * (hi[1] - lo[1]) + (hi[2] - lo[2]) * (hi[2] - lo[2]));
-    std::vector<double> S((size_t)(HL_GRID + 1) * (HL_GRID + 1) * n);          // scores of every vertex at the grid points of one face
-    std::vector<double> cn((size_t)(HL_GRID + 1) * (HL_GRID + 1));
-    for (int face = 0; face < 6; face++) {
-      int ax = face / 2; double sg = (face & 1) ? -1.0 : 1.0;
-      for (int iu = 0; iu <= HL_GRID; iu++)
-        for (int iv = 0; iv <= HL_GRID; iv++) {
-          double c[3]; c[ax] = sg; c[(ax + 1) % 3] = -1.0 + 2.0 * iu / HL_GRID; c[(ax + 2) % 3] = -1.0 + 2.0 * iv / HL_GRID;
-          size_t pt = (size_t)iu * (HL_GRID + 1) + iv;
-          cn[pt] = std::sqrt(c[0] * c[0] + c[1] * c[1] + c[2] * c[2]);
-          double* sp = &S[pt * n];
-          for (int k = 0; k < n; k++) sp[k] = V[3 * k] * c[0] + V[3 * k + 1] * c[1] + V[3 * k + 2] * c[2];
-        }
-      for (int iu = 0; iu < HL_GRID; iu++)
-        for (int iv = 0; iv < HL_GRID; iv++) {
-          const size_t pts[4] = {(size_t)iu * (HL_GRID + 1) + iv, (size_t)(iu + 1) * (HL_GRID + 1) + iv, (size_t)iu * (HL_GRID + 1) + iv + 1, (size_t)(iu + 1) * (HL_GRID + 1) + iv + 1};
-          int win[4]; double eps[4];
-          for (int q = 0; q < 4; q++) {
-            const double* sp = &S[pts[q] * n]; int w = 0;
-            for (int k = 1; k < n; k++) if (sp[k] > sp[w]) w = k;
-            win[q] = w; eps[q] = 4e-3 * diam * cn[pts[q]] + 1e-6;
-          }
-          off[(face * HL_GRID + iu) * HL_GRID + iv] = (unsigned int)(hle.size() / 4);
-          for (int k = 0; k < n; k++) {
-            bool keep = true;
-            for (int w = 0; w < 4 && keep; w++) {            // beaten by corner winner w at ALL four corners by more than the widening: out
-              bool some = false;
-              for (int q = 0; q < 4; q++) some = some || S[pts[q] * n + k] >= S[pts[q] * n + win[w]] - eps[q];
-              keep = some;
-            }
-            if (keep) { hle.push_back(V[3 * k]); hle.push_back(V[3 * k + 1]); hle.push_back(V[3 * k + 2]); float fi; unsigned int ui = (unsigned int)k; memcpy(&fi, &ui, 4); hle.push_back(fi); }
-          }
-        }
-    }
-    off[HL_CELLS] = (unsigned int)(hle.size() / 4);
+    build_support_lists(&mv[3 * (size_t)gva[g]], gvn[g], hle, off);
   }
   M.hl_entry = nullptr; M.hl_off = nullptr;
   if (!hl_off_env && !(upload(s, hle, &M.hl_entry) && upload(s, hlo, &M.hl_off))) return SO101_ERR_HIP;

@@ -4,6 +4,7 @@
 #include "so101_blob.hpp"
 #include "../../include/so101.h"
 #include "so101_tree.hpp"
+#include "so101_tables.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -530,6 +531,10 @@ int tree_build(TreeHandle* s, const BlobView& b) {
       !in_range("act_dof", nv) || !in_range("eq_dof", nv) || !in_range("eq_qposadr", M.nq)) return fail("blob index array out of range");
   auto gva = b.I("geom_vertadr"), gvn = b.I("geom_vertnum");
   for (size_t g = 0; g < ng; g++) if (gvn[g] > 0 && (gva[g] < 0 || (size_t)gva[g] + (size_t)gvn[g] > (size_t)nvert)) return fail("geom vertex range outside mesh_vert");
+  {
+    auto gty = b.I("geom_type");              // (the support tables and every support query of a hull need at least one vertex)
+    for (size_t g = 0; g < ng; g++) if (gty[g] == G_MESH && gvn[g] <= 0) return fail("mesh geom without vertices (geom_vertnum <= 0)");
+  }
   for (float v : b.F("geom_margin")) if (v != 0.f) return fail("geom margin must be 0");
   for (float v : b.F("geom_gap")) if (v != 0.f) return fail("geom gap must be 0");
 
@@ -615,24 +620,10 @@ int tree_build(TreeHandle* s, const BlobView& b) {
     if (gtype[g1] > gtype[g2]) std::swap(g1, g2);
     packed[p] = (unsigned)g1 | ((unsigned)g2 << 8) | (gtype[g1] == G_PLANE ? 1u << 16 : 0u);
   }
-  // support-bound tables of the hulls (so101_model.hpp DevModel::hull_sbt): in double, rounded up to float
+  // support-bound tables of the hulls (so101_model.hpp DevModel::hull_sbt; so101_tables.hpp)
   std::vector<float> sbt((size_t)ng * SBT_DIM, 0.f);
-  for (size_t g = 0; g < ng; g++) {
-    if (gtype[g] != G_MESH) continue;
-    for (int face = 0; face < 6; face++) {
-      int ax = face / 2; double sg = (face & 1) ? -1.0 : 1.0;
-      for (int iu = 0; iu < SBT_GRID; iu++)
-        for (int iv = 0; iv < SBT_GRID; iv++) {
-          const double step = 2.0 / (SBT_GRID - 1);
-          double c[3]; c[ax] = sg; c[(ax + 1) % 3] = -1.0 + step * iu; c[(ax + 2) % 3] = -1.0 + step * iv;
-          double best = -1e300;
-          for (int k = gva[g]; k < gva[g] + gvn[g]; k++) best = std::max(best, (double)mv[3 * k] * c[0] + (double)mv[3 * k + 1] * c[1] + (double)mv[3 * k + 2] * c[2]);
-          float f = (float)best;
-          if ((double)f < best) f = std::nextafterf(f, 3.0e38f);
-          sbt[g * SBT_DIM + (face * SBT_GRID + iu) * SBT_GRID + iv] = f;
-        }
-    }
-  }
+  for (size_t g = 0; g < ng; g++)
+    if (gtype[g] == G_MESH) build_support_bounds(&mv[3 * (size_t)gva[g]], gvn[g], &sbt[g * SBT_DIM]);
   G.hull_sbt = nullptr;
   bool ok = (getenv("SO101_NO_SBT") != nullptr || t_upload(s, sbt, &G.hull_sbt)) &&
             t_upload(s, gtype, &G.geom_type) && t_upload(s, b.I("geom_body"), &G.geom_dyn) && t_upload(s, b.I("geom_condim"), &G.geom_condim) &&

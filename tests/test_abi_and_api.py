@@ -31,6 +31,34 @@ def test_create_rejects_bad_blobs_without_gpu(hip_lib, blobs):
         native.Sim(blobs["f32"][:4000], 4)
     lib = native.load_library()
     assert lib.so101_configure(None, None) == -1 and lib.so101_step(None, None, None, None, None, None, None) == -1
+    # a mesh geom without vertices (the support tables and queries need one): rejected by the model check, which runs after the device
+    # is made current - so through the emulated build of the same source (tests/hostemu), which needs no GPU
+    from tests.simharness import build_emu
+    emu = build_emu()
+    for n in (0, -1):
+        with pytest.raises(RuntimeError, match=r"so101_create failed \(-2\): mesh geom without vertices"):
+            native.Sim(_with_mesh_vertnum(blobs["f32"], n), 4, lib_path=emu)
+
+
+def _with_mesh_vertnum(raw, n):
+    """the blob with geom_vertnum of its first mesh geom set to n"""
+    from so101_sim_amd.model import blob as blobfmt
+    m = blobfmt.unpack(raw)
+    vn = m["geom_vertnum"].copy()
+    vn[int(np.flatnonzero(m["geom_type"] == 5)[0])] = n
+    m["geom_vertnum"] = vn
+    return blobfmt.pack(m)
+
+
+def test_tree_create_rejects_mesh_without_vertices_without_gpu():
+    from so101_sim_amd import native
+    from so101_sim_amd.model import scenes
+    from tests.simharness import build_emu
+    emu = build_emu()
+    raw = scenes.load_aloha_blob("banana", "f32")[0]
+    for n in (0, -1):
+        with pytest.raises(RuntimeError, match=r"so101_tree_create failed \(-2\): mesh geom without vertices"):
+            native.TreeSim(_with_mesh_vertnum(raw, n), 4, lib_path=emu)
 
 
 def test_missing_library_fails_loudly(tmp_path):
