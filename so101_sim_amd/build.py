@@ -21,7 +21,7 @@ LIB_CLOCKS = os.path.join(CSRC, "libso101_hip_clocks.so")     # -DSO101_DEBUG_CL
 LIB_EXP = os.path.join(CSRC, "libso101_hip_exp.so")           # -DSO101_EXPERIMENTAL_PIPELINES: the default library plus the two step paths that were built, proven bit-identical and measured
                                                               # slower than the launch chains (pipeline = 2 per-env chaining, 3 merged launches); built on demand
 LIB_MPR = os.path.join(CSRC, "libso101_hip_mpr.so")           # -DSO101_MPR: the narrowphase="mpr" option - MPR's own portal depth instead of the EPA expansion to the nearest face that the
-                                                              # default library runs (so101_device.hpp); built on demand, not by __graft_entry__.build()
+                                                              # default library runs (so101_geom.hpp); built on demand, not by __graft_entry__.build()
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -fno-hip-fp32-correctly-rounded-divide-sqrt: v_rcp/v_sqrt based fp32 division and sqrt (<= ~2.5 ulp) instead of
 # the 10-15 instruction IEEE expansions; the solver is latency-bound and full of both (profiles/README.md).

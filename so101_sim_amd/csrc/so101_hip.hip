@@ -1,10 +1,8 @@
 // libso101_hip.so — C ABI (include/so101.h) over the gfx950 kernels.  Host side: blob parsing, device
 // copy of the model, launch plumbing.  No torch types, no CPU compute path: every entry point that
 // does physics launches a HIP kernel or fails.
-#include "so101_blob.hpp"
-#include "../../include/so101.h"
+#include "so101_host.hpp"
 #include "so101_launch.hpp"
-#include "so101_tables.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -20,12 +18,6 @@ namespace {
 
 thread_local std::string g_create_error;
 
-void h_quat2mat(float* m, const float* q) {
-  float w = q[0], x = q[1], y = q[2], z = q[3];
-  m[0] = 1 - 2 * (y * y + z * z); m[1] = 2 * (x * y - w * z); m[2] = 2 * (x * z + w * y);
-  m[3] = 2 * (x * y + w * z); m[4] = 1 - 2 * (x * x + z * z); m[5] = 2 * (y * z - w * x);
-  m[6] = 2 * (x * z - w * y); m[7] = 2 * (y * z + w * x); m[8] = 1 - 2 * (x * x + y * y);
-}
 void h_mulquat(float* o, const float* a, const float* b) {
   float t[4] = {a[0] * b[0] - a[1] * b[1] - a[2] * b[2] - a[3] * b[3], a[0] * b[1] + a[1] * b[0] + a[2] * b[3] - a[3] * b[2],
                 a[0] * b[2] - a[1] * b[3] + a[2] * b[0] + a[3] * b[1], a[0] * b[3] + a[1] * b[2] - a[2] * b[1] + a[3] * b[0]};
@@ -46,12 +38,11 @@ void h_inertia(float* o, const float* iquat, const float* diag, bool inverse) {
 
 }  // namespace
 
-struct so101_sim {
-  int n_envs = 0, device = 0;
+struct so101_sim : HostHandle {      // (so101_host.hpp: device, owned allocations, err)
+  int n_envs = 0;
   uint64_t seed = 0;
   DevModel hm{};               // host copy (device pointers inside)
   DevModel* dm = nullptr;      // device copy
-  std::vector<void*> owned;    // device allocations to free
   so101_config cfg{};
   DevBuffers buf{};
   bool bound = false;
@@ -87,40 +78,9 @@ struct so101_sim {
   int last_path = -1, last_chains = 0;                  // so101_get_info
   bool last_graph = false;
   size_t scratch_bytes = 0;
-  std::string err;
 };
 
 namespace {
-
-bool hip_ok(so101_sim* s, hipError_t e, const char* what) {
-  if (e == hipSuccess) return true;
-  s->err = std::string(what) + ": " + hipGetErrorString(e);
-  return false;
-}
-
-// Every entry point that touches HIP runs with the handle's device current and restores the caller's device on exit
-// (a handle is bound to one device; streams, events and allocations below belong to it).
-struct DeviceGuard {
-  int prev = -1, dev;
-  bool ok;
-  explicit DeviceGuard(so101_sim* s) : dev(s->device) {
-    ok = hipGetDevice(&prev) == hipSuccess && (prev == dev || hipSetDevice(dev) == hipSuccess);
-    if (!ok) s->err = "hipSetDevice: cannot make the handle's device current";
-  }
-  ~DeviceGuard() { if (prev >= 0 && prev != dev) (void)hipSetDevice(prev); }
-};
-#define GUARD_DEVICE(s) DeviceGuard guard_(s); if (!guard_.ok) return SO101_ERR_HIP
-
-template <typename T>
-bool upload(so101_sim* s, const std::vector<T>& v, const T** out) {
-  void* p = nullptr;
-  size_t bytes = std::max<size_t>(v.size(), 1) * sizeof(T);
-  if (!hip_ok(s, hipMalloc(&p, bytes), "hipMalloc(model)")) return false;
-  s->owned.push_back(p);
-  if (!v.empty() && !hip_ok(s, hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice), "hipMemcpy(model)")) return false;
-  *out = (const T*)p;
-  return true;
-}
 
 StepParams make_params(const so101_sim* s) {
   StepParams P{};
@@ -145,10 +105,9 @@ int build_model(so101_sim* s, const BlobView& b) {
   for (const char* n : scalars) if (b.count(n) < 1) return fail(std::string("blob entry missing: ") + n);
   {
     // every array the code below indexes, with the element count it relies on: a stale or foreign blob is rejected
-    // here instead of being dereferenced
-    size_t nbody = (size_t)b.I("nbody")[0], ngeom = (size_t)b.I("ngeom")[0], npair = (size_t)b.I("npair")[0], nvert = (size_t)b.I("nvert")[0];
-    size_t nbox = (size_t)b.I("task_nbox")[0];
-    if (nbody > 4096 || ngeom > 4096 || npair > (1u << 24) || nvert > (1u << 24) || nbox > 2) return fail("blob dimensions out of range");
+    // here instead of being dereferenced (the geom_* / mesh_vert / pair_geom entries: check_geometry() below)
+    size_t nbody = (size_t)b.I("nbody")[0], nbox = (size_t)b.I("task_nbox")[0];
+    if (nbody > 4096 || nbox > 2) return fail("blob dimensions out of range");
     struct Need { const char* name; size_t count; };
     const Need arrays[] = {
       {"arm_body", NARM}, {"free_body", NFREE}, {"body_parent", nbody}, {"body_jnttype", nbody}, {"body_pos", 3 * nbody}, {"body_quat", 4 * nbody},
@@ -158,29 +117,21 @@ int build_model(so101_sim* s, const BlobView& b) {
       {"jnt_solimp", 5 * NARM}, {"dof_solref", 2 * NARM}, {"dof_solimp", 5 * NARM}, {"act_gain", NU}, {"act_bias", 3 * NU},
       {"act_ctrlrange", 2 * NU}, {"act_forcerange", 2 * NU}, {"act_ctrllimited", NU}, {"act_forcelimited", NU}, {"act_dof", NU},
       {"task_box_pos", 3 * nbox}, {"task_box_half", 3 * nbox}, {"task_obj_pos_lo", 3}, {"task_obj_pos_hi", 3}, {"task_obj_yaw", 2},
-      {"task_con_pos_lo", 3}, {"task_con_pos_hi", 3}, {"task_home_ctrl", NU}, {"geom_type", ngeom}, {"geom_body", ngeom}, {"geom_condim", ngeom},
-      {"geom_vertadr", ngeom}, {"geom_vertnum", ngeom}, {"geom_pos", 3 * ngeom}, {"geom_quat", 4 * ngeom}, {"geom_size", 3 * ngeom},
-      {"geom_friction", 3 * ngeom}, {"geom_solref", 2 * ngeom}, {"geom_solimp", 5 * ngeom}, {"geom_center", 3 * ngeom}, {"geom_aabb", 6 * ngeom},
-      {"geom_solmix", ngeom}, {"geom_margin", ngeom}, {"geom_gap", ngeom}, {"geom_priority", ngeom}, {"geom_rbound", ngeom}, {"mesh_vert", 3 * nvert}, {"pair_geom", 2 * npair}};
+      {"task_con_pos_lo", 3}, {"task_con_pos_hi", 3}, {"task_home_ctrl", NU}};
     for (const Need& a : arrays) if (b.count(a.name) < a.count) return fail(std::string("blob entry missing or too short: ") + a.name);
     auto in_range = [&](const char* name, size_t limit, bool allow_negative) {
       for (int v : b.I(name)) if ((v < 0 && !allow_negative) || (v >= 0 && (size_t)v >= limit)) return false;
       return true;
     };
     if (!in_range("arm_body", nbody, false) || !in_range("free_body", nbody, false) || !in_range("body_parent", nbody, false) ||
-        !in_range("geom_body", nbody, false) || !in_range("pair_geom", ngeom, false) || !in_range("task_object_body", nbody, false) ||
-        !in_range("task_container_body", nbody, false)) return fail("blob index array out of range");
-    auto gva = b.I("geom_vertadr"), gvn = b.I("geom_vertnum"), gty = b.I("geom_type");
-    for (size_t g = 0; g < ngeom; g++) if (gvn[g] > 0 && (gva[g] < 0 || (size_t)gva[g] + (size_t)gvn[g] > nvert)) return fail("geom vertex range outside mesh_vert");
-    // (the support tables and every support query of a hull need at least one vertex)
-    for (size_t g = 0; g < ngeom; g++) if (gty[g] == G_MESH && gvn[g] <= 0) return fail("mesh geom without vertices (geom_vertnum <= 0)");
+        !in_range("task_object_body", nbody, false) || !in_range("task_container_body", nbody, false)) return fail("blob index array out of range");
   }
   DevModel& M = s->hm;
   int nq = b.I("nq")[0], nv = b.I("nv")[0], nu = b.I("nu")[0], nbody = b.I("nbody")[0], ngeom = b.I("ngeom")[0];
   int narm = b.I("narm")[0], nfree = b.I("nfree")[0];
   if (narm != NARM || nfree != NFREE || nq != NQ || nv != NV || nu != NU)
     return fail("model topology outside this build (need a 6-hinge chain and 2 free bodies)");
-  if (ngeom > MAXGEOM) return fail("too many collision geoms for this build");
+  if (!check_geometry(b, (size_t)nbody, MAXGEOM, s->err)) return SO101_ERR_MODEL;
   auto arm_body = b.I("arm_body"), free_body = b.I("free_body"), parent = b.I("body_parent"), jt = b.I("body_jnttype");
   auto bpos = b.F("body_pos"), bquat = b.F("body_quat"), ipos = b.F("body_ipos"), iquat = b.F("body_iquat");
   auto mass = b.F("body_mass"), inertia = b.F("body_inertia"), invw = b.F("body_invweight0"), bvh = b.F("body_bvh_aabb");
@@ -203,7 +154,6 @@ int build_model(so101_sim* s, const BlobView& b) {
   int base = parent[arm_body[0]];
   for (int k = 0; k < 3; k++) M.base_pos[k] = wpos[3 * base + k];
   for (int k = 0; k < 4; k++) M.base_quat[k] = wquat[4 * base + k];
-  M.ngeom = ngeom; M.npair = b.I("npair")[0]; M.nvert = b.I("nvert")[0];
   M.iterations = b.I("opt_iterations")[0]; M.mpr_iter = b.I("opt_mpr_iterations")[0]; M.nbox = b.I("task_nbox")[0];
   if (M.nbox > 2) return fail("at most 2 overlap boxes");
   if (!b.I("opt_cone_elliptic")[0]) return fail("only elliptic cones are implemented (scene_pbr.xml:4)");
@@ -257,11 +207,8 @@ int build_model(so101_sim* s, const BlobView& b) {
   M.obj_yaw[0] = oy[0]; M.obj_yaw[1] = oy[1];
   for (int i = 0; i < NU; i++) M.home_ctrl[i] = hc[i];
   // geoms: dynamic ones keep body-local frames, static ones are resolved to world frames here
-  auto gtype = b.I("geom_type"), gbody = b.I("geom_body"), gcondim = b.I("geom_condim"), gva = b.I("geom_vertadr"), gvn = b.I("geom_vertnum");
-  auto gpos = b.F("geom_pos"), gquat = b.F("geom_quat"), gsize = b.F("geom_size"), gfr = b.F("geom_friction"), gsr = b.F("geom_solref");
-  auto gsi = b.F("geom_solimp"), gctr = b.F("geom_center"), gaabb = b.F("geom_aabb"), gmix = b.F("geom_solmix"), gmargin = b.F("geom_margin"), ggap = b.F("geom_gap");
-  auto gprio = b.I("geom_priority");
-  auto grb = b.F("geom_rbound");
+  auto gbody = b.I("geom_body"), gprio = b.I("geom_priority");
+  auto gpos = b.F("geom_pos"), gquat = b.F("geom_quat"), gmix = b.F("geom_solmix"), gmargin = b.F("geom_margin"), ggap = b.F("geom_gap");
   std::vector<int> gdyn(ngeom);
   std::vector<float> gp(3 * ngeom), gm(9 * ngeom);
   for (int i = 0; i < ngeom; i++) {
@@ -279,47 +226,8 @@ int build_model(so101_sim* s, const BlobView& b) {
       for (int k = 0; k < 3; k++) gp[3 * i + k] = wpos[3 * bi + k] + R[3 * k] * gpos[3 * i] + R[3 * k + 1] * gpos[3 * i + 1] + R[3 * k + 2] * gpos[3 * i + 2];
     }
   }
-  auto mv = b.F("mesh_vert");
-  int nvert = M.nvert;
-  std::vector<float> vx(nvert), vy(nvert), vz(nvert);
-  for (int i = 0; i < nvert; i++) { vx[i] = mv[3 * i]; vy[i] = mv[3 * i + 1]; vz[i] = mv[3 * i + 2]; }
-  auto pairs = b.I("pair_geom");
-  // broadphase pair list, one word per pair: geom1 | geom2 << 8 | (geom1 is a plane) << 16, geom types ordered
-  std::vector<unsigned int> packed(M.npair);
-  for (int k = 0; k < M.npair; k++) {
-    int g1 = pairs[2 * k], g2 = pairs[2 * k + 1];
-    if (gtype[g1] > gtype[g2]) std::swap(g1, g2);
-    packed[k] = (unsigned int)g1 | ((unsigned int)g2 << 8) | ((gtype[g1] == G_PLANE ? 1u : 0u) << 16);
-  }
-  // support-bound tables of the hulls (so101_model.hpp DevModel::hull_sbt, obb_filter; so101_tables.hpp)
-  std::vector<float> sbt((size_t)ngeom * SBT_DIM, 0.f);
-  for (int g = 0; g < ngeom; g++)
-    if (gtype[g] == G_MESH) build_support_bounds(&mv[3 * (size_t)gva[g]], gvn[g], &sbt[(size_t)g * SBT_DIM]);
-  // support-vertex lists (so101_model.hpp DevModel::hl_entry): per hull and cube-map cell the vertices that can win a support query there
-  std::vector<float> hle; std::vector<unsigned int> hlo((size_t)ngeom * (HL_CELLS + 1), 0u);
-  const bool hl_off_env = getenv("SO101_NO_HL") != nullptr;          // (tests and kernel experiments: every query scans the whole hull, as until round 6)
-  for (int g = 0; g < ngeom; g++) {
-    unsigned int* off = &hlo[(size_t)g * (HL_CELLS + 1)];
-    if (gtype[g] != G_MESH || hl_off_env) { for (int c = 0; c <= HL_CELLS; c++) off[c] = (unsigned int)(hle.size() / 4); continue; }
-    build_support_lists(&mv[3 * (size_t)gva[g]], gvn[g], hle, off);
-  }
-  M.hl_entry = nullptr; M.hl_off = nullptr;
-  if (!hl_off_env && !(upload(s, hle, &M.hl_entry) && upload(s, hlo, &M.hl_off))) return SO101_ERR_HIP;
-  const bool sbt_off = getenv("SO101_NO_SBT") != nullptr;          // (tests and kernel experiments, read at every so101_create: the oriented-box filter alone, as until round 5)
-  M.hull_sbt = nullptr;
-  bool ok = (sbt_off || upload(s, sbt, &M.hull_sbt)) &&
-            upload(s, gtype, &M.geom_type) && upload(s, gdyn, &M.geom_dyn) && upload(s, gcondim, &M.geom_condim) &&
-            upload(s, gva, &M.geom_vertadr) && upload(s, gvn, &M.geom_vertnum) && upload(s, gp, &M.geom_pos) &&
-            upload(s, gm, &M.geom_mat) && upload(s, gsize, &M.geom_size) && upload(s, gfr, &M.geom_friction) &&
-            upload(s, gsr, &M.geom_solref) && upload(s, gsi, &M.geom_solimp) && upload(s, gctr, &M.geom_center) &&
-            upload(s, gaabb, &M.geom_aabb) && upload(s, grb, &M.geom_rbound) && upload(s, vx, &M.vx) && upload(s, vy, &M.vy) && upload(s, vz, &M.vz) &&
-            upload(s, pairs, &M.pair) && upload(s, packed, &M.pair_packed);
-  if (!ok) return SO101_ERR_HIP;
-  void* dm = nullptr;
-  if (!hip_ok(s, hipMalloc(&dm, sizeof(DevModel)), "hipMalloc(DevModel)")) return SO101_ERR_HIP;
-  s->owned.push_back(dm);
-  if (!hip_ok(s, hipMemcpy(dm, &M, sizeof(DevModel), hipMemcpyHostToDevice), "hipMemcpy(DevModel)")) return SO101_ERR_HIP;
-  s->dm = (DevModel*)dm;
+  // everything else of the geometry is the same in both engines (so101_host.hpp); this one's k_narrow reads the support-vertex lists
+  if (!upload_geometry(s, b, gdyn, gp, gm, true, M) || !upload_one(s, M, &s->dm)) return SO101_ERR_HIP;
   return SO101_OK;
 }
 
@@ -366,15 +274,10 @@ PrepBuffers prep_view(const so101_sim* s) {
   return C;
 }
 
-template <typename T>
-bool dev_alloc(so101_sim* s, T** out, size_t count, int fill, const char* what) {
-  void* p = nullptr;
-  size_t bytes = sizeof(T) * (count ? count : 1);
-  if (!hip_ok(s, hipMalloc(&p, bytes), what)) return false;
-  s->owned.push_back(p);
-  s->scratch_bytes += bytes;
-  if (!hip_ok(s, hipMemset(p, fill, bytes), what)) return false;
-  *out = (T*)p;
+template <typename T>       // dev_alloc() of so101_host.hpp, counted for SO101_INFO_SCRATCH_BYTES
+bool scratch_alloc(so101_sim* s, T** out, size_t count, int fill, const char* what) {
+  if (!dev_alloc(s, out, count, fill, what)) return false;
+  s->scratch_bytes += sizeof(T) * (count ? count : 1);
   return true;
 }
 
@@ -410,15 +313,15 @@ int so101_create(const void* blob, size_t bytes, int n_envs, int device, uint64_
   if (rc == SO101_OK) rc = build_model(s, b);
   size_t n = (size_t)n_envs;
   if (rc == SO101_OK) {
-    bool ok = dev_alloc(s, &s->need_reset, n, 1, "hipMalloc(need_reset)") && dev_alloc(s, &s->diag, SO101_DIAG_DIM * n, 0, "hipMalloc(diag)") &&
-              dev_alloc(s, &s->ev.flags, n, 0, "hipMalloc(events)") && dev_alloc(s, &s->ev.events, (size_t)SO101_NEVENTS, 0, "hipMalloc(events)");
+    bool ok = scratch_alloc(s, &s->need_reset, n, 1, "hipMalloc(need_reset)") && scratch_alloc(s, &s->diag, SO101_DIAG_DIM * n, 0, "hipMalloc(diag)") &&
+              scratch_alloc(s, &s->ev.flags, n, 0, "hipMalloc(events)") && scratch_alloc(s, &s->ev.events, (size_t)SO101_NEVENTS, 0, "hipMalloc(events)");
     if (!ok) rc = SO101_ERR_HIP;
   }
   if (rc == SO101_OK) {
     PrepBuffers& C = s->prep;
-    bool ok = dev_alloc(s, &C.qpos, 2 * NQ * n, 0, "hipMalloc(prep)") && dev_alloc(s, &C.qvel, 2 * NV * n, 0, "hipMalloc(prep)") &&
-              dev_alloc(s, &C.warm, 2 * NV * n, 0, "hipMalloc(prep)") && dev_alloc(s, &C.tag, 2 * n, 0xFF, "hipMalloc(prep)") &&
-              dev_alloc(s, &C.cursor, (size_t)2, 0, "hipMalloc(prep)") && dev_alloc(s, &C.flags, 2 * n, 0, "hipMalloc(prep)");
+    bool ok = scratch_alloc(s, &C.qpos, 2 * NQ * n, 0, "hipMalloc(prep)") && scratch_alloc(s, &C.qvel, 2 * NV * n, 0, "hipMalloc(prep)") &&
+              scratch_alloc(s, &C.warm, 2 * NV * n, 0, "hipMalloc(prep)") && scratch_alloc(s, &C.tag, 2 * n, 0xFF, "hipMalloc(prep)") &&
+              scratch_alloc(s, &C.cursor, (size_t)2, 0, "hipMalloc(prep)") && scratch_alloc(s, &C.flags, 2 * n, 0, "hipMalloc(prep)");
     int lo = 0, hi = 0;
     ok = ok && hip_ok(s, hipDeviceGetStreamPriorityRange(&lo, &hi), "hipDeviceGetStreamPriorityRange") &&
          hip_ok(s, hipStreamCreateWithPriority(&s->prep_stream, hipStreamNonBlocking, lo), "hipStreamCreateWithPriority") &&
@@ -429,22 +332,22 @@ int so101_create(const void* blob, size_t bytes, int n_envs, int device, uint64_
   }
   if (rc == SO101_OK) {
     PipeBuffers& W = s->pipe;
-    bool ok = dev_alloc(s, &W.pose, NDYN * 12 * n, 0, "hipMalloc(pipe)") && dev_alloc(s, &W.cand, MAXCAND * n, 0, "hipMalloc(pipe)") &&
-              dev_alloc(s, &W.ncand, n, 0, "hipMalloc(pipe)") && dev_alloc(s, &W.items, ITEM_WORDS * (CONRES_PER_ENV * n + (size_t)MAXCAND * so101_sim::MAXGROUPS), 0, "hipMalloc(pipe)") &&
-              dev_alloc(s, &W.counters, (size_t)4 * MAXSUB * so101_sim::MAXGROUPS, 0, "hipMalloc(pipe)") &&
-              dev_alloc(s, &W.conres, CONRES_DIM * (CONRES_PER_ENV * n + (size_t)MAXCAND * so101_sim::MAXGROUPS), 0, "hipMalloc(pipe)") && dev_alloc(s, &W.cbase, n, 0, "hipMalloc(pipe)") &&
-              dev_alloc(s, &W.active, n, 0, "hipMalloc(pipe)") &&
+    bool ok = scratch_alloc(s, &W.pose, NDYN * 12 * n, 0, "hipMalloc(pipe)") && scratch_alloc(s, &W.cand, MAXCAND * n, 0, "hipMalloc(pipe)") &&
+              scratch_alloc(s, &W.ncand, n, 0, "hipMalloc(pipe)") && scratch_alloc(s, &W.items, ITEM_WORDS * (CONRES_PER_ENV * n + (size_t)MAXCAND * so101_sim::MAXGROUPS), 0, "hipMalloc(pipe)") &&
+              scratch_alloc(s, &W.counters, (size_t)4 * MAXSUB * so101_sim::MAXGROUPS, 0, "hipMalloc(pipe)") &&
+              scratch_alloc(s, &W.conres, CONRES_DIM * (CONRES_PER_ENV * n + (size_t)MAXCAND * so101_sim::MAXGROUPS), 0, "hipMalloc(pipe)") && scratch_alloc(s, &W.cbase, n, 0, "hipMalloc(pipe)") &&
+              scratch_alloc(s, &W.active, n, 0, "hipMalloc(pipe)") &&
 #ifdef SO101_DEBUG_CLOCKS
-              dev_alloc(s, &W.ticks, MAXCAND * n, 0, "hipMalloc(pipe)") &&
+              scratch_alloc(s, &W.ticks, MAXCAND * n, 0, "hipMalloc(pipe)") &&
 #else
-              dev_alloc(s, &W.ticks, (size_t)1, 0, "hipMalloc(pipe)") &&
+              scratch_alloc(s, &W.ticks, (size_t)1, 0, "hipMalloc(pipe)") &&
 #endif
-              dev_alloc(s, &W.stage, 8 * n, 0, "hipMalloc(pipe)") &&
-              dev_alloc(s, &W.cost, n, 0, "hipMalloc(pipe)") && dev_alloc(s, &W.order, n, 0, "hipMalloc(pipe)") &&
-              dev_alloc(s, &W.state, STATE_AOS * n, 0, "hipMalloc(pipe)") &&
-              dev_alloc(s, &s->chain.pending, n, 0, "hipMalloc(chain)") && dev_alloc(s, &s->chain_cls, n, 0, "hipMalloc(chain)") &&
-              dev_alloc(s, &s->chain.qctl, (size_t)4 * 64, 0, "hipMalloc(chain)") && dev_alloc(s, &s->chain.chain_ctl, (size_t)64, 0, "hipMalloc(chain)") &&
-              dev_alloc(s, &s->chain_params, (size_t)1, 0, "hipMalloc(chain)") && dev_alloc(s, &s->chain.stats, (size_t)16, 0, "hipMalloc(chain)");
+              scratch_alloc(s, &W.stage, 8 * n, 0, "hipMalloc(pipe)") &&
+              scratch_alloc(s, &W.cost, n, 0, "hipMalloc(pipe)") && scratch_alloc(s, &W.order, n, 0, "hipMalloc(pipe)") &&
+              scratch_alloc(s, &W.state, STATE_AOS * n, 0, "hipMalloc(pipe)") &&
+              scratch_alloc(s, &s->chain.pending, n, 0, "hipMalloc(chain)") && scratch_alloc(s, &s->chain_cls, n, 0, "hipMalloc(chain)") &&
+              scratch_alloc(s, &s->chain.qctl, (size_t)4 * 64, 0, "hipMalloc(chain)") && scratch_alloc(s, &s->chain.chain_ctl, (size_t)64, 0, "hipMalloc(chain)") &&
+              scratch_alloc(s, &s->chain_params, (size_t)1, 0, "hipMalloc(chain)") && scratch_alloc(s, &s->chain.stats, (size_t)16, 0, "hipMalloc(chain)");
     s->chain.cls = s->chain_cls;
     s->chain.idle_sleeps = getenv("SO101_CHAIN_IDLE") ? atoi(getenv("SO101_CHAIN_IDLE")) : 8;
     s->chain.role_mode = getenv("SO101_CHAIN_ROLE") ? atoi(getenv("SO101_CHAIN_ROLE")) : 0;
@@ -483,7 +386,7 @@ void so101_destroy(so101_sim* s) {
     if (s->step_begin) (void)hipEventDestroy(s->step_begin);
     if (s->prep_done) (void)hipEventDestroy(s->prep_done);
     if (s->main_ev) (void)hipEventDestroy(s->main_ev);
-    for (void* p : s->owned) (void)hipFree(p);
+    free_owned(s);
   }
   delete s;
 }
@@ -709,17 +612,17 @@ static int enqueue_pipelined(so101_sim* s, hipStream_t st, const so101::StepIO& 
 static bool ensure_experimental_buffers(so101_sim* s) {
   if (s->conres_full) return true;
   size_t n = (size_t)s->n_envs;
-  bool ok = dev_alloc(s, &s->conres_full, CONRES_DIM * MAXCAND * n, 0, "hipMalloc(chain)");
+  bool ok = scratch_alloc(s, &s->conres_full, CONRES_DIM * MAXCAND * n, 0, "hipMalloc(chain)");
   // merged launches: one chunk ring per chain (capacity: the next power of two above 64 chunks per env of the chain, so a ring
   // can never wrap onto live granules), head / avail / tail words and per-launch counters per chain
   size_t cap = 64; while (cap < 2 * n * (MAXCAND / NARROW_CHUNK)) cap <<= 1;
-  ok = ok && dev_alloc(s, &s->mq_slot, cap, 0, "hipMalloc(merged)") && dev_alloc(s, &s->mq_ctl, (size_t)64 * so101_sim::MAXGROUPS, 0, "hipMalloc(merged)") &&
-       dev_alloc(s, &s->mq_pub, (size_t)128 * so101_sim::MAXGROUPS, 0, "hipMalloc(merged)");
+  ok = ok && scratch_alloc(s, &s->mq_slot, cap, 0, "hipMalloc(merged)") && scratch_alloc(s, &s->mq_ctl, (size_t)64 * so101_sim::MAXGROUPS, 0, "hipMalloc(merged)") &&
+       scratch_alloc(s, &s->mq_pub, (size_t)128 * so101_sim::MAXGROUPS, 0, "hipMalloc(merged)");
   // chained step: narrow chunks (at most MAXCAND / NARROW_CHUNK outstanding per env), solve items (one per env)
   for (int q = 0; q < 4 && ok; q++) {
     size_t need = q < Q_SOLVE ? n * (MAXCAND / NARROW_CHUNK) : n, c = 64;
     while (c < need) c <<= 1;
-    ok = dev_alloc(s, &s->chain.qslot[q], c, 0, "hipMalloc(chain)");
+    ok = scratch_alloc(s, &s->chain.qslot[q], c, 0, "hipMalloc(chain)");
     s->chain.qmask[q] = (unsigned int)(c - 1);
   }
   if (!ok) s->conres_full = nullptr;

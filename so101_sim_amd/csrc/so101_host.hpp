@@ -1,0 +1,152 @@
+// Host layer shared by the two engines' handles (so101_sim of so101_hip.hip, TreeHandle of tu_tree.hip): device guard, HIP error
+// helper, owned device allocations, and the loader that puts a model blob's collision geometry into a DevModel.  Host code only.
+// The general-tree engine is compiled twice (tu_tree.hip inside tv32 / tv64) and the emulator build of the tests includes every .hip
+// into one translation unit: everything here is inline, outside those namespaces, and depends on no T* macro.
+#pragma once
+#include <hip/hip_runtime.h>
+#include "so101_blob.hpp"
+#include "../../include/so101.h"
+#include "so101_tables.hpp"
+
+#include <algorithm>
+#include <cstdlib>
+#include <string>
+#include <vector>
+
+// what every handle carries: its device, the device allocations it owns, its last error message
+struct HostHandle {
+  int device = 0;
+  std::vector<void*> owned;
+  std::string err;
+};
+
+inline bool hip_ok(HostHandle* s, hipError_t e, const char* what) {
+  if (e == hipSuccess) return true;
+  s->err = std::string(what) + ": " + hipGetErrorString(e);
+  return false;
+}
+
+// Every entry point that touches HIP runs with the handle's device current and restores the caller's device on exit
+// (a handle is bound to one device; its streams, events and allocations belong to it).
+struct DeviceGuard {
+  int prev = -1, dev;
+  bool ok;
+  explicit DeviceGuard(HostHandle* s) : dev(s->device) {
+    ok = hipGetDevice(&prev) == hipSuccess && (prev == dev || hipSetDevice(dev) == hipSuccess);
+    if (!ok) s->err = "hipSetDevice: cannot make the handle's device current";
+  }
+  ~DeviceGuard() { if (prev >= 0 && prev != dev) (void)hipSetDevice(prev); }
+};
+#define GUARD_DEVICE(s) DeviceGuard guard_(s); if (!guard_.ok) return SO101_ERR_HIP
+
+// `count` elements (at least one) owned by the handle, every byte set to `fill` (fill < 0: left as hipMalloc returns them)
+template <typename T>
+bool dev_alloc(HostHandle* s, T** out, size_t count, int fill, const char* what) {
+  void* p = nullptr;
+  size_t bytes = sizeof(T) * (count ? count : 1);
+  if (!hip_ok(s, hipMalloc(&p, bytes), what)) return false;
+  s->owned.push_back(p);
+  if (fill >= 0 && !hip_ok(s, hipMemset(p, fill, bytes), what)) return false;
+  *out = (T*)p;
+  return true;
+}
+
+// device copy of a host array / of one struct, owned by the handle
+template <typename T>
+bool upload(HostHandle* s, const std::vector<T>& v, const T** out) {
+  T* p = nullptr;
+  if (!dev_alloc(s, &p, v.size(), -1, "hipMalloc(model)")) return false;
+  if (!v.empty() && !hip_ok(s, hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice), "hipMemcpy(model)")) return false;
+  *out = p;
+  return true;
+}
+template <typename T>
+bool upload_one(HostHandle* s, const T& v, T** out) {
+  return dev_alloc(s, out, 1, -1, "hipMalloc(model)") && hip_ok(s, hipMemcpy(*out, &v, sizeof(T), hipMemcpyHostToDevice), "hipMemcpy(model)");
+}
+
+inline void free_owned(HostHandle* s) {
+  for (void* p : s->owned) (void)hipFree(p);
+  s->owned.clear();
+}
+
+inline void h_quat2mat(float* m, const float* q) {
+  float w = q[0], x = q[1], y = q[2], z = q[3];
+  m[0] = 1 - 2 * (y * y + z * z); m[1] = 2 * (x * y - w * z); m[2] = 2 * (x * z + w * y);
+  m[3] = 2 * (x * y + w * z); m[4] = 1 - 2 * (x * x + z * z); m[5] = 2 * (y * z - w * x);
+  m[6] = 2 * (x * z - w * y); m[7] = 2 * (y * z + w * x); m[8] = 1 - 2 * (x * x + y * y);
+}
+
+// ---------------------------------------------------------------------------------------------------- geometry of a model blob
+// The geom_* / mesh_vert / pair_geom entries of a blob whose scalars ngeom, npair and nvert exist (the engines check their scalars first):
+// every array the loader and the engines index is there with the length they rely on, geom_body and pair_geom are in range, vertex ranges
+// lie inside mesh_vert.  ngeom_max: the engine's ceiling (at most 256: a packed pair word carries a geom in 8 bits).  A stale or foreign
+// blob is rejected here instead of being dereferenced; false with the message in `err`.
+inline bool check_geometry(const BlobView& b, size_t nbody, size_t ngeom_max, std::string& err) {
+  auto fail = [&](const std::string& msg) { err = msg; return false; };
+  size_t ng = (size_t)b.I("ngeom")[0], np = (size_t)b.I("npair")[0], nvert = (size_t)b.I("nvert")[0];
+  if (ng > ngeom_max) return fail("too many collision geoms for this build");
+  if (np > (1u << 24) || nvert > (1u << 24)) return fail("blob dimensions out of range");
+  struct Need { const char* name; size_t count; };
+  const Need arrays[] = {
+    {"geom_type", ng}, {"geom_body", ng}, {"geom_condim", ng}, {"geom_vertadr", ng}, {"geom_vertnum", ng}, {"geom_pos", 3 * ng}, {"geom_quat", 4 * ng},
+    {"geom_size", 3 * ng}, {"geom_friction", 3 * ng}, {"geom_solref", 2 * ng}, {"geom_solimp", 5 * ng}, {"geom_center", 3 * ng}, {"geom_aabb", 6 * ng},
+    {"geom_solmix", ng}, {"geom_margin", ng}, {"geom_gap", ng}, {"geom_priority", ng}, {"geom_rbound", ng}, {"mesh_vert", 3 * nvert}, {"pair_geom", 2 * np}};
+  for (const Need& a : arrays) if (b.count(a.name) < a.count) return fail(std::string("blob entry missing or too short: ") + a.name);
+  for (int v : b.I("geom_body")) if (v < 0 || (size_t)v >= nbody) return fail("blob index array out of range");
+  for (int v : b.I("pair_geom")) if (v < 0 || (size_t)v >= ng) return fail("blob index array out of range");
+  auto gva = b.I("geom_vertadr"), gvn = b.I("geom_vertnum"), gty = b.I("geom_type");
+  for (size_t g = 0; g < ng; g++) if (gvn[g] > 0 && (gva[g] < 0 || (size_t)gva[g] + (size_t)gvn[g] > nvert)) return fail("geom vertex range outside mesh_vert");
+  // (the support tables and every support query of a hull need at least one vertex)
+  for (size_t g = 0; g < ng; g++) if (gty[g] == G_MESH && gvn[g] <= 0) return fail("mesh geom without vertices (geom_vertnum <= 0)");
+  return true;
+}
+
+// Every geometry pointer of M, and ngeom / npair / nvert, from a blob that passed check_geometry().  The engine supplies what differs between
+// the two: geom_dyn (SO100: index of the dynamic body or -1; tree: body id) and the geoms' frames geom_pos [g][3] / geom_mat [g][9] (SO100:
+// static geoms resolved to the world; tree: body-local).  Built here: the packed pair words, the vertices as struct-of-arrays, the hulls'
+// support-bound tables and - support_lists: the SO100 engine's k_narrow reads them, the tree engine does not and keeps hl_entry / hl_off
+// NULL - their support-vertex lists (so101_tables.hpp).  SO101_NO_SBT / SO101_NO_HL in the environment (tests and kernel experiments, read at
+// every create) leave hull_sbt / hl_entry and hl_off NULL: the oriented-box filter alone, every query scans the whole hull.
+// false: a HIP call failed (s->err).
+inline bool upload_geometry(HostHandle* s, const BlobView& b, const std::vector<int>& geom_dyn, const std::vector<float>& geom_pos, const std::vector<float>& geom_mat,
+                            bool support_lists, DevModel& M) {
+  M.ngeom = b.I("ngeom")[0]; M.npair = b.I("npair")[0]; M.nvert = b.I("nvert")[0];
+  const int ngeom = M.ngeom, nvert = M.nvert;
+  auto gtype = b.I("geom_type"), gva = b.I("geom_vertadr"), gvn = b.I("geom_vertnum"), pairs = b.I("pair_geom");
+  auto mv = b.F("mesh_vert");
+  std::vector<float> vx(nvert), vy(nvert), vz(nvert);
+  for (int i = 0; i < nvert; i++) { vx[i] = mv[3 * i]; vy[i] = mv[3 * i + 1]; vz[i] = mv[3 * i + 2]; }
+  // broadphase pair list, one word per pair: geom1 | geom2 << 8 | (geom1 is a plane) << 16, geom types ordered
+  std::vector<unsigned int> packed(M.npair);
+  for (int k = 0; k < M.npair; k++) {
+    int g1 = pairs[2 * k], g2 = pairs[2 * k + 1];
+    if (gtype[g1] > gtype[g2]) std::swap(g1, g2);
+    packed[k] = (unsigned int)g1 | ((unsigned int)g2 << 8) | ((gtype[g1] == G_PLANE ? 1u : 0u) << 16);
+  }
+  // support-bound tables of the hulls (so101_model.hpp DevModel::hull_sbt; obb_filter and the tree's broadphase)
+  M.hull_sbt = nullptr;
+  if (!getenv("SO101_NO_SBT")) {
+    std::vector<float> sbt((size_t)ngeom * SBT_DIM, 0.f);
+    for (int g = 0; g < ngeom; g++)
+      if (gtype[g] == G_MESH) build_support_bounds(&mv[3 * (size_t)gva[g]], gvn[g], &sbt[(size_t)g * SBT_DIM]);
+    if (!upload(s, sbt, &M.hull_sbt)) return false;
+  }
+  // support-vertex lists (so101_model.hpp DevModel::hl_entry): per hull and cube-map cell the vertices that can win a support query there
+  M.hl_entry = nullptr; M.hl_off = nullptr;
+  if (support_lists && !getenv("SO101_NO_HL")) {
+    std::vector<float> hle; std::vector<unsigned int> hlo((size_t)ngeom * (HL_CELLS + 1), 0u);
+    for (int g = 0; g < ngeom; g++) {
+      unsigned int* off = &hlo[(size_t)g * (HL_CELLS + 1)];
+      if (gtype[g] != G_MESH) { for (int c = 0; c <= HL_CELLS; c++) off[c] = (unsigned int)(hle.size() / 4); continue; }
+      build_support_lists(&mv[3 * (size_t)gva[g]], gvn[g], hle, off);
+    }
+    if (!(upload(s, hle, &M.hl_entry) && upload(s, hlo, &M.hl_off))) return false;
+  }
+  return upload(s, gtype, &M.geom_type) && upload(s, geom_dyn, &M.geom_dyn) && upload(s, b.I("geom_condim"), &M.geom_condim) &&
+         upload(s, gva, &M.geom_vertadr) && upload(s, gvn, &M.geom_vertnum) && upload(s, geom_pos, &M.geom_pos) && upload(s, geom_mat, &M.geom_mat) &&
+         upload(s, b.F("geom_size"), &M.geom_size) && upload(s, b.F("geom_friction"), &M.geom_friction) && upload(s, b.F("geom_solref"), &M.geom_solref) &&
+         upload(s, b.F("geom_solimp"), &M.geom_solimp) && upload(s, b.F("geom_center"), &M.geom_center) && upload(s, b.F("geom_aabb"), &M.geom_aabb) &&
+         upload(s, b.F("geom_rbound"), &M.geom_rbound) && upload(s, vx, &M.vx) && upload(s, vy, &M.vy) && upload(s, vz, &M.vz) &&
+         upload(s, pairs, &M.pair) && upload(s, packed, &M.pair_packed);
+}

@@ -68,13 +68,13 @@ struct DevModel {
   // grid points c of the cube [-1, 1]^3's faces (face 2 a + (sign < 0), u and v in steps of 0.5 along axes a + 1, a + 2), rounded up.  The support
   // function is convex and positively homogeneous, so for any direction d the bilinear interpolation over the four grid points around
   // d / |d|_inf, times |d|_inf, is an UPPER bound of h(d) - a few per cent of the hull's size above it, against the tens of per cent of an
-  // oriented box around a curved shell piece.  Built at so101_create from the blob's vertices (so101_hip.hip); used by obb_filter.
+  // oriented box around a curved shell piece.  Built at create from the blob's vertices (so101_host.hpp); used by obb_filter and the tree engine's broadphase.
   const float* hull_sbt;
   // support-vertex lists of the mesh geoms (round 6; NULL: none).  The cube-map of directions is cut into 6 x HL_GRID x HL_GRID cells; hl_off[g * (HL_CELLS
   // + 1) + c] .. [.. + c + 1] is the range of cell c's entries in hl_entry, four floats each: x, y, z of a vertex (the floats of vx / vy / vz) and its
   // index within the hull (bits).  A cell's list holds, in increasing index order, every vertex that can be the support point for SOME direction of the
   // cell widened by 4e-3 rad: a vertex v is left out only when one of the four vertices that win at the cell's corners beats it at all four corners by
-  // more than the widening - then it loses everywhere in between by linearity (so101_hip.hip).  Median 10-17 of a hull's 200-1080 vertices.
+  // more than the widening - then it loses everywhere in between by linearity (so101_tables.hpp).  Median 10-17 of a hull's 200-1080 vertices.
   const float* hl_entry;
   const unsigned int* hl_off;
 };

@@ -122,7 +122,7 @@ DEV void publish_candidates(const DevModel* m, const EnvLDS& L, const PipeBuffer
       GeomW G1, G2;
       item_put_geom(m, L, g1, it + ITEM_GEOM0, G1); item_put_geom(m, L, g2, it + ITEM_GEOM1, G2);
       // round 6: a flat face against a hull - the cell of the hull's support-vertex lists that the query's first support direction falls into, so
-      // that k_narrow can fetch those few vertices right behind the item instead of staging the whole hull (so101_device.hpp HullSub); word 46 = first
+      // that k_narrow can fetch those few vertices right behind the item instead of staging the whole hull (so101_geom.hpp HullSub); word 46 = first
       // entry, word 47 = entries (1 .. HL_MAX) | cell << 8, or 0: none
       it[46] = 0u; it[47] = 0u;
       if (m->hl_off) {

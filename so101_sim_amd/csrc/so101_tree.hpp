@@ -5,9 +5,10 @@
 // One env = one wavefront, as everywhere in this library, but nothing here is specialised: lanes take bodies, dofs,
 // constraint rows or contacts in turn, matrices live in LDS, the constraint Jacobian in a per-env global scratch.  It is the
 // FIRST GPU path for these scenes, written for parity with the fp64 CPU restatement used by the tests (the same stages in the
-// same order); the SO100 kernels of so101_device.hpp / so101_newton.hpp stay the fast path for the headline workload.
-// The narrowphase (support functions, flat-face scan, MPR, patch contacts) is shared with them.
-#include "so101_device.hpp"
+// same order); the SO100 engine (so101_env.hpp, so101_newton.hpp) stays the fast path for the headline workload.
+// The narrowphase (support functions, flat-face scan, MPR, patch contacts) is shared with them: so101_geom.hpp, and the small math
+// under it (so101_math.hpp).  Nothing else of the SO100 engine is visible here.
+#include "so101_geom.hpp"
 
 // Two builds of this file share one library (csrc/tu_tree.hip, csrc/tu_tree64.hip; TREE_VARIANT), each inside its own namespace:
 //   32 (ALOHA hand-over): 32 dofs, 40 positions, 128 geoms, 64 contacts, 384 rows - LDS 40 KB per env (25 KB + the constraint
@@ -607,7 +608,7 @@ DEV int broadphase(const TreeModel* tm, const DevModel* gm, TreeLDS& L) {
   wave_sync();
   int ncand = base;
   if (ncand > TCAND) { ncand = TCAND; if (lane == 0) L.flags |= 1; }
-  // Second pass, lane = candidate (as obb_filter of so101_device.hpp for the SO100 scenes): separating-axis test of the two geoms'
+  // Second pass, lane = candidate (as obb_filter of the SO100 engine for its scenes): separating-axis test of the two geoms'
   // ORIENTED boxes (15 axes).  The world box of a long tilted arm link overlaps many hulls it is nowhere near; a pair whose oriented
   // boxes are more than 1e-6 m apart cannot touch, so dropping it changes no contact - it spares the wavefront a narrowphase query that
   // would end in "no intersection" (of the ALOHA scenes' 34 candidates per env about half).  Plane pairs pass.  Order kept.
@@ -649,7 +650,7 @@ DEV int broadphase(const TreeModel* tm, const DevModel* gm, TreeLDS& L) {
               sep = sep || fabsf(t[i2] * Rm[i1][j] - t[i1] * Rm[i2][j]) > ra + rb + gap;
             }
           keep = !sep;
-          // round 6: further separating directions from the hulls' support-bound tables (so101_device.hpp sbt_separated)
+          // round 6: further separating directions from the hulls' support-bound tables (so101_geom.hpp sbt_separated)
           if (keep && gm->hull_sbt && gm->geom_type[g2] == G_MESH) {
             float cwa[3] = {pa[0] + ca[0], pa[1] + ca[1], pa[2] + ca[2]}, cwb[3] = {pb[0] + cb[0], pb[1] + cb[1], pb[2] + cb[2]};
             keep = !sbt_separated(gm, g1, g2, A, cwa, a, Bm, cwb, t);

@@ -5,7 +5,7 @@
 #include "so101_pipeline.hpp"
 #include "so101_launch.hpp"
 
-// One wavefront per candidate pair (policy G64 of so101_device.hpp), persistent wavefronts pulling chunks of work items.
+// One wavefront per candidate pair (policy G64 of so101_geom.hpp), persistent wavefronts pulling chunks of work items.
 //
 // Round 5: memory round trips per CHUNK instead of five to seven per pair.  A chunk is 2 (heavy region) or 4 (light region) self-contained
 // items (so101_pipeline.hpp: both geoms in world coordinates, hull addresses, the record position); a wavefront takes
@@ -15,7 +15,7 @@
 //   3. EVERY hull of the chunk into LDS at once (up to HULL_POOL vertex slots of the workgroup's 20 KB share; loads of all hulls in flight
 //      together), and then works through the pairs without touching memory again until the records are written.  A hull that did not fit
 //      is staged when its pair's turn comes (over the slots of the pairs already done).
-// Support scans read the staged hulls with ds_read_b128 (so101_device.hpp, HullLDS); the register hull cache of rounds 2-4 (48 VGPRs, 43
+// Support scans read the staged hulls with ds_read_b128 (so101_geom.hpp, HullLDS); the register hull cache of rounds 2-4 (48 VGPRs, 43
 // more spilled to scratch: 14 MB written per launch) is gone from this kernel, the kernel has no scratch.
 //
 // Measured alternative (kept as policy G16, bit-identical results): one pair per DPP row of 16 lanes, four pairs per
@@ -47,7 +47,7 @@ __global__ void __launch_bounds__(64, NarrowCfg<ROWS>::waves) k_narrow(const Dev
   constexpr int HULL_POOL = NarrowCfg<ROWS>::pool;          // vertex slots of the LDS hull pool: 256 or 512 per staged hull
   __shared__ __attribute__((aligned(16))) float pool[3 * HULL_POOL];
   // the row pass: every row reads its own item.  (Shares its storage with the values the full-wave query parks across MPR / EPA -
-  // narrow_park_store() of so101_device.hpp -: the row pass runs the closed forms only and parks nothing, and its items are dead before
+  // narrow_park_store() of so101_geom.hpp -: the row pass runs the closed forms only and parks nothing, and its items are dead before
   // the full-wave loop starts.)
   unsigned int* row_items = (unsigned int*)narrow_park_store();
   static_assert(NARROW_CHUNK * ITEM_WORDS <= NARROW_PARK_WORDS, "the row items must fit the park area");

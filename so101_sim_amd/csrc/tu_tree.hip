@@ -1,10 +1,8 @@
 // General-tree engine (so101_tree.hpp): kernels and the so101_tree_* entry points of include/so101.h.
 // Kernels and their launches live in one translation unit (no relocatable device code).
 #include <hip/hip_runtime.h>
-#include "so101_blob.hpp"
-#include "../../include/so101.h"
+#include "so101_host.hpp"
 #include "so101_tree.hpp"
-#include "so101_tables.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -322,7 +320,7 @@ __global__ void __launch_bounds__(64) k_tree_pipe_begin(const TreeModel* tm, con
 }
 
 // one wavefront per candidate pair of the whole batch: persistent wavefronts take two work items per fetch
-// (round 5: the hulls of a pair are staged in LDS - so101_device.hpp, HullLDS - instead of held in 48 VGPRs; with the hull patches inlined the register
+// (round 5: the hulls of a pair are staged in LDS - so101_geom.hpp, HullLDS - instead of held in 48 VGPRs; with the hull patches inlined the register
 //  cache left this kernel 55 spilled VGPRs and 184 B of scratch per lane)
 __global__ void __launch_bounds__(64, 2) k_tree_narrow(const TreeModel* tm, const DevModel* gm, TreePipe P, int N, int s) {
   __shared__ __attribute__((aligned(16))) float pool[3 * 2 * HULL_LDS_MAX];
@@ -437,8 +435,8 @@ __global__ void __launch_bounds__(64, 2) k_tree_pipe_finish(const TreeModel* tm,
 }
 
 // ==================================================================================================== host side
-struct TreeHandle {
-  int n_envs = 0, device = 0;
+struct TreeHandle : HostHandle {      // (so101_host.hpp: device, owned allocations, err)
+  int n_envs = 0;
   TreeModel hm{};
   DevModel hg{};
   TreeModel* dm = nullptr;
@@ -462,45 +460,10 @@ struct TreeHandle {
   hipStream_t slice_stream[MAXSLICES] = {};      // env slices whose chains overlap (one's narrowphase beside another's solve)
   hipEvent_t slice_begin = nullptr, slice_done[MAXSLICES] = {};
   int plan[4] = {0, 0, 0, 0};          // what the last so101_tree_step enqueued: env slices, kernel launches, memsets, path (0 none yet, 1 single kernel, 2 launch chain)
-  std::vector<void*> owned;
-  std::string err;
 };
 
 namespace {
 thread_local std::string g_tree_error;
-
-// every entry point that touches HIP runs with the handle's device current and restores the caller's device on exit
-struct TreeDeviceGuard {
-  int prev = -1, dev;
-  bool ok;
-  explicit TreeDeviceGuard(TreeHandle* s) : dev(s->device) {
-    ok = hipGetDevice(&prev) == hipSuccess && (prev == dev || hipSetDevice(dev) == hipSuccess);
-    if (!ok) s->err = "hipSetDevice: cannot make the handle's device current";
-  }
-  ~TreeDeviceGuard() { if (prev >= 0 && prev != dev) (void)hipSetDevice(prev); }
-};
-#define TREE_GUARD(s) TreeDeviceGuard guard_(s); if (!guard_.ok) return SO101_ERR_HIP
-
-void tq2m(float* m, const float* q) {
-  float w = q[0], x = q[1], y = q[2], z = q[3];
-  m[0] = 1 - 2 * (y * y + z * z); m[1] = 2 * (x * y - w * z); m[2] = 2 * (x * z + w * y);
-  m[3] = 2 * (x * y + w * z); m[4] = 1 - 2 * (x * x + z * z); m[5] = 2 * (y * z - w * x);
-  m[6] = 2 * (x * z - w * y); m[7] = 2 * (y * z + w * x); m[8] = 1 - 2 * (x * x + y * y);
-}
-bool t_ok(TreeHandle* s, hipError_t e, const char* what) {
-  if (e == hipSuccess) return true;
-  s->err = std::string(what) + ": " + hipGetErrorString(e);
-  return false;
-}
-template <class T>
-bool t_upload(TreeHandle* s, const std::vector<T>& v, const T** out) {
-  void* p = nullptr;
-  if (!t_ok(s, hipMalloc(&p, (v.size() ? v.size() : 1) * sizeof(T)), "hipMalloc(tree model)")) return false;
-  s->owned.push_back(p);
-  if (!v.empty() && !t_ok(s, hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice), "hipMemcpy(tree model)")) return false;
-  *out = (const T*)p;
-  return true;
-}
 
 int tree_build(TreeHandle* s, const BlobView& b) {
   auto fail = [&](const std::string& msg) { s->err = msg; return (int)SO101_ERR_MODEL; };
@@ -510,10 +473,9 @@ int tree_build(TreeHandle* s, const BlobView& b) {
   TreeModel& M = s->hm;
   M.nq = b.I("nq")[0]; M.nv = b.I("nv")[0]; M.nu = b.I("nu")[0]; M.nbody = b.I("nbody")[0]; M.ngeom = b.I("ngeom")[0];
   M.npair = b.I("npair")[0]; M.njnt = b.I("narm")[0]; M.nfree = b.I("nfree")[0]; M.neq = b.I("neq")[0];
-  int nvert = b.I("nvert")[0];
   if (M.nq > TQ || M.nv > TV || M.nu > TU || M.nbody > TB || M.ngeom > TGEOM || M.njnt > TJ || M.neq > TE || M.nq < 0 || M.nv < 0 || M.nbody < 1)
     return fail("model dimensions outside the general-tree builds (32 bodies, 64 dofs, 64 positions, 16 actuators, 256 geoms)");
-  size_t nb = M.nbody, ng = M.ngeom, nv = M.nv, nj = M.njnt, nu = M.nu, ne = M.neq, np = M.npair;
+  size_t nb = M.nbody, ng = M.ngeom, nv = M.nv, nj = M.njnt, nu = M.nu, ne = M.neq;
   struct Need { const char* name; size_t count; };
   const Need arrays[] = {
     {"body_parent", nb}, {"body_jnttype", nb}, {"body_qposadr", nb}, {"body_dofadr", nb}, {"body_pos", 3 * nb}, {"body_quat", 4 * nb}, {"body_ipos", 3 * nb},
@@ -521,20 +483,12 @@ int tree_build(TreeHandle* s, const BlobView& b) {
     {"dof_damping", nv}, {"dof_frictionloss", nv}, {"dof_invweight0", nv}, {"dof_solref", 2 * nj}, {"dof_solimp", 5 * nj}, {"jnt_axis", 3 * nj}, {"jnt_range", 2 * nj},
     {"jnt_limited", nj}, {"jnt_solref", 2 * nj}, {"jnt_solimp", 5 * nj}, {"jnt_actfrclimited", nj}, {"jnt_actfrcrange", 2 * nj}, {"act_dof", nu}, {"act_gain", nu},
     {"act_bias", 3 * nu}, {"act_ctrlrange", 2 * nu}, {"act_forcerange", 2 * nu}, {"act_ctrllimited", nu}, {"act_forcelimited", nu}, {"eq_dof", 2 * ne},
-    {"eq_qposadr", 2 * ne}, {"eq_polycoef", 5 * ne}, {"eq_solref", 2 * ne}, {"eq_solimp", 5 * ne}, {"opt_gravity", 3}, {"geom_type", ng}, {"geom_body", ng},
-    {"geom_condim", ng}, {"geom_vertadr", ng}, {"geom_vertnum", ng}, {"geom_pos", 3 * ng}, {"geom_quat", 4 * ng}, {"geom_size", 3 * ng}, {"geom_friction", 3 * ng},
-    {"geom_solref", 2 * ng}, {"geom_solimp", 5 * ng}, {"geom_center", 3 * ng}, {"geom_aabb", 6 * ng}, {"geom_solmix", ng}, {"geom_priority", ng}, {"geom_rbound", ng},
-    {"geom_margin", ng}, {"geom_gap", ng}, {"mesh_vert", 3 * (size_t)nvert}, {"pair_geom", 2 * np}};
+    {"eq_qposadr", 2 * ne}, {"eq_polycoef", 5 * ne}, {"eq_solref", 2 * ne}, {"eq_solimp", 5 * ne}, {"opt_gravity", 3}};
   for (const Need& a : arrays) if (b.count(a.name) < a.count) return fail(std::string("blob entry missing or too short: ") + a.name);
   auto in_range = [&](const char* name, size_t limit) { for (int v : b.I(name)) if (v < 0 || (size_t)v >= limit) return false; return true; };
-  if (!in_range("body_parent", nb) || !in_range("geom_body", nb) || !in_range("pair_geom", ng) || !in_range("arm_body", nb) || !in_range("dof_body", nb) ||
+  if (!in_range("body_parent", nb) || !in_range("arm_body", nb) || !in_range("dof_body", nb) ||
       !in_range("act_dof", nv) || !in_range("eq_dof", nv) || !in_range("eq_qposadr", M.nq)) return fail("blob index array out of range");
-  auto gva = b.I("geom_vertadr"), gvn = b.I("geom_vertnum");
-  for (size_t g = 0; g < ng; g++) if (gvn[g] > 0 && (gva[g] < 0 || (size_t)gva[g] + (size_t)gvn[g] > (size_t)nvert)) return fail("geom vertex range outside mesh_vert");
-  {
-    auto gty = b.I("geom_type");              // (the support tables and every support query of a hull need at least one vertex)
-    for (size_t g = 0; g < ng; g++) if (gty[g] == G_MESH && gvn[g] <= 0) return fail("mesh geom without vertices (geom_vertnum <= 0)");
-  }
+  if (!check_geometry(b, nb, TGEOM, s->err)) return SO101_ERR_MODEL;          // (the geom_* / mesh_vert / pair_geom entries: so101_host.hpp)
   for (float v : b.F("geom_margin")) if (v != 0.f) return fail("geom margin must be 0");
   for (float v : b.F("geom_gap")) if (v != 0.f) return fail("geom gap must be 0");
 
@@ -605,36 +559,16 @@ int tree_build(TreeHandle* s, const BlobView& b) {
 
   // geometry: the tables the shared narrowphase reads (DevModel), every geom relative to its body
   DevModel& G = s->hg;
-  G.ngeom = M.ngeom; G.npair = M.npair; G.nvert = nvert; G.iterations = M.iterations; G.mpr_iter = b.I("opt_mpr_iterations")[0];
+  G.iterations = M.iterations; G.mpr_iter = b.I("opt_mpr_iterations")[0];
   G.dt = M.dt; G.mpr_tol = b.F("opt_mpr_tolerance")[0]; G.impratio = M.impratio; G.tolerance = M.tolerance; G.meaninertia = M.meaninertia;
   auto gquat = b.F("geom_quat");
   std::vector<float> gmat(9 * ng);
-  for (size_t g = 0; g < ng; g++) tq2m(&gmat[9 * g], &gquat[4 * g]);
-  auto mv = b.F("mesh_vert");
-  std::vector<float> vx(nvert), vy(nvert), vz(nvert);
-  for (int i = 0; i < nvert; i++) { vx[i] = mv[3 * i]; vy[i] = mv[3 * i + 1]; vz[i] = mv[3 * i + 2]; }
-  auto gtype = b.I("geom_type"), pairs = b.I("pair_geom");
-  std::vector<unsigned int> packed(np);
-  for (size_t p = 0; p < np; p++) {
-    int g1 = pairs[2 * p], g2 = pairs[2 * p + 1];
-    if (gtype[g1] > gtype[g2]) std::swap(g1, g2);
-    packed[p] = (unsigned)g1 | ((unsigned)g2 << 8) | (gtype[g1] == G_PLANE ? 1u << 16 : 0u);
-  }
-  // support-bound tables of the hulls (so101_model.hpp DevModel::hull_sbt; so101_tables.hpp)
-  std::vector<float> sbt((size_t)ng * SBT_DIM, 0.f);
-  for (size_t g = 0; g < ng; g++)
-    if (gtype[g] == G_MESH) build_support_bounds(&mv[3 * (size_t)gva[g]], gvn[g], &sbt[g * SBT_DIM]);
-  G.hull_sbt = nullptr;
-  bool ok = (getenv("SO101_NO_SBT") != nullptr || t_upload(s, sbt, &G.hull_sbt)) &&
-            t_upload(s, gtype, &G.geom_type) && t_upload(s, b.I("geom_body"), &G.geom_dyn) && t_upload(s, b.I("geom_condim"), &G.geom_condim) &&
-            t_upload(s, gva, &G.geom_vertadr) && t_upload(s, gvn, &G.geom_vertnum) && t_upload(s, b.F("geom_pos"), &G.geom_pos) && t_upload(s, gmat, &G.geom_mat) &&
-            t_upload(s, b.F("geom_size"), &G.geom_size) && t_upload(s, b.F("geom_friction"), &G.geom_friction) && t_upload(s, b.F("geom_solref"), &G.geom_solref) &&
-            t_upload(s, b.F("geom_solimp"), &G.geom_solimp) && t_upload(s, b.F("geom_center"), &G.geom_center) && t_upload(s, b.F("geom_aabb"), &G.geom_aabb) &&
-            t_upload(s, b.F("geom_rbound"), &G.geom_rbound) && t_upload(s, vx, &G.vx) && t_upload(s, vy, &G.vy) && t_upload(s, vz, &G.vz) &&
-            t_upload(s, pairs, &G.pair) && t_upload(s, packed, &G.pair_packed) && t_upload(s, b.I("geom_body"), &M.geom_body) &&
-            t_upload(s, b.F("geom_solmix"), &M.geom_solmix) && t_upload(s, b.I("geom_priority"), &M.geom_priority);
+  for (size_t g = 0; g < ng; g++) h_quat2mat(&gmat[9 * g], &gquat[4 * g]);
+  // (geom_dyn = the body id; no support-vertex lists: k_tree_narrow scans the staged hulls)
+  bool ok = upload_geometry(s, b, b.I("geom_body"), b.F("geom_pos"), gmat, false, G) && upload(s, b.I("geom_body"), &M.geom_body) &&
+            upload(s, b.F("geom_solmix"), &M.geom_solmix) && upload(s, b.I("geom_priority"), &M.geom_priority);
   M.geom_class = nullptr;
-  if (ok && b.count("task_geom_class") >= ng) ok = t_upload(s, b.I("task_geom_class"), &M.geom_class);
+  if (ok && b.count("task_geom_class") >= ng) ok = upload(s, b.I("task_geom_class"), &M.geom_class);
   if (!ok) return SO101_ERR_HIP;
   // task layer (hand-over scenes): absent from the bare-arm blob
   TreeTask& T = s->task;
@@ -678,13 +612,7 @@ int tree_build(TreeHandle* s, const BlobView& b) {
     for (int k = 0; k < M.njnt; k++) T.home_qpos[k] = hq[k];
     for (int k = 0; k < M.nu; k++) T.home_ctrl[k] = hc[k];
   }
-  void* p = nullptr;
-  if (!t_ok(s, hipMalloc(&p, sizeof(TreeModel)), "hipMalloc(TreeModel)")) return SO101_ERR_HIP;
-  s->owned.push_back(p); s->dm = (TreeModel*)p;
-  if (!t_ok(s, hipMemcpy(p, &M, sizeof(TreeModel), hipMemcpyHostToDevice), "hipMemcpy(TreeModel)")) return SO101_ERR_HIP;
-  if (!t_ok(s, hipMalloc(&p, sizeof(DevModel)), "hipMalloc(DevModel)")) return SO101_ERR_HIP;
-  s->owned.push_back(p); s->dg = (DevModel*)p;
-  if (!t_ok(s, hipMemcpy(p, &G, sizeof(DevModel), hipMemcpyHostToDevice), "hipMemcpy(DevModel)")) return SO101_ERR_HIP;
+  if (!upload_one(s, M, &s->dm) || !upload_one(s, G, &s->dg)) return SO101_ERR_HIP;
   return SO101_OK;
 }
 }  // namespace
@@ -700,44 +628,34 @@ static TreeStore store_now(TreeHandle* s) {
 static bool tree_prefetch_setup(TreeHandle* s) {          // lazily: second scratch, cache, low-priority stream
   if (s->ctag) return true;
   size_t n = (size_t)s->n_envs;
-  auto alloc = [&](void** out, size_t bytes) {
-    void* p = nullptr;
-    if (!t_ok(s, hipMalloc(&p, bytes), "hipMalloc(prefetch)")) return false;
-    s->owned.push_back(p); *out = p;
-    return t_ok(s, hipMemset(p, 0, bytes), "hipMemset(prefetch)");
-  };
   int lo = 0, hi = 0;
   (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
-  return alloc((void**)&s->scratch2, n * T_SCRATCH * sizeof(float)) && alloc((void**)&s->cq, n * s->hm.nq * sizeof(float)) &&
-         alloc((void**)&s->cv, n * s->hm.nv * sizeof(float)) && alloc((void**)&s->cw, n * s->hm.nv * sizeof(float)) && alloc((void**)&s->cf, n * sizeof(int)) &&
-         t_ok(s, hipStreamCreateWithPriority(&s->prep_stream, hipStreamNonBlocking, lo), "hipStreamCreateWithPriority") &&
-         t_ok(s, hipEventCreateWithFlags(&s->prep_done, hipEventDisableTiming), "hipEventCreate") &&
-         t_ok(s, hipEventCreateWithFlags(&s->main_ev, hipEventDisableTiming), "hipEventCreate") && alloc((void**)&s->ctag, n * sizeof(unsigned int));
+  const char* what = "hipMalloc(prefetch)";
+  return dev_alloc(s, &s->scratch2, n * T_SCRATCH, 0, what) && dev_alloc(s, &s->cq, n * s->hm.nq, 0, what) &&
+         dev_alloc(s, &s->cv, n * s->hm.nv, 0, what) && dev_alloc(s, &s->cw, n * s->hm.nv, 0, what) && dev_alloc(s, &s->cf, n, 0, what) &&
+         hip_ok(s, hipStreamCreateWithPriority(&s->prep_stream, hipStreamNonBlocking, lo), "hipStreamCreateWithPriority") &&
+         hip_ok(s, hipEventCreateWithFlags(&s->prep_done, hipEventDisableTiming), "hipEventCreate") &&
+         hip_ok(s, hipEventCreateWithFlags(&s->main_ev, hipEventDisableTiming), "hipEventCreate") && dev_alloc(s, &s->ctag, n, 0, what);
 }
 static bool tree_pipe_setup(TreeHandle* s) {             // lazily: the hand-off buffers of the launch chain
   if (s->pipe.pose) return true;
   size_t n = (size_t)s->n_envs;
-  auto alloc = [&](void** out, size_t bytes) {
-    void* p = nullptr;
-    if (!t_ok(s, hipMalloc(&p, bytes), "hipMalloc(pipeline)")) return false;
-    s->owned.push_back(p); *out = p;
-    return t_ok(s, hipMemset(p, 0, bytes), "hipMemset(pipeline)");
-  };
   TreePipe& P = s->pipe;
-  void* pose = nullptr;
-  bool ok = alloc((void**)&P.cand, n * TCAND * sizeof(unsigned int)) && alloc((void**)&P.ncand, n * sizeof(int)) && alloc((void**)&P.rec, n * TCAND * TREC * sizeof(float)) &&
-            alloc((void**)&P.work, 2 * n * TCAND * sizeof(unsigned int)) && alloc((void**)&P.counters, TreeHandle::MAXSLICES * 2 * TPIPE_MAXSUB * sizeof(int)) && alloc((void**)&P.active, n) &&
-            alloc((void**)&P.pflags, n * sizeof(int)) && alloc((void**)&P.pdiag, 4 * n * sizeof(int)) && alloc(&pose, n * TB * 12 * sizeof(float));
+  float* pose = nullptr;
+  const char* what = "hipMalloc(pipeline)";
+  bool ok = dev_alloc(s, &P.cand, n * TCAND, 0, what) && dev_alloc(s, &P.ncand, n, 0, what) && dev_alloc(s, &P.rec, n * TCAND * TREC, 0, what) &&
+            dev_alloc(s, &P.work, 2 * n * TCAND, 0, what) && dev_alloc(s, &P.counters, (size_t)TreeHandle::MAXSLICES * 2 * TPIPE_MAXSUB, 0, what) && dev_alloc(s, &P.active, n, 0, what) &&
+            dev_alloc(s, &P.pflags, n, 0, what) && dev_alloc(s, &P.pdiag, 4 * n, 0, what) && dev_alloc(s, &pose, n * TB * 12, 0, what);
   for (int g = 0; ok && g < TreeHandle::MAXSLICES; g++)
-    ok = t_ok(s, hipStreamCreateWithFlags(&s->slice_stream[g], hipStreamNonBlocking), "hipStreamCreate") &&
-         t_ok(s, hipEventCreateWithFlags(&s->slice_done[g], hipEventDisableTiming), "hipEventCreate");
-  ok = ok && t_ok(s, hipEventCreateWithFlags(&s->slice_begin, hipEventDisableTiming), "hipEventCreate");
-  if (ok) P.pose = (float*)pose;          // (last: marks the set as complete)
+    ok = hip_ok(s, hipStreamCreateWithFlags(&s->slice_stream[g], hipStreamNonBlocking), "hipStreamCreate") &&
+         hip_ok(s, hipEventCreateWithFlags(&s->slice_done[g], hipEventDisableTiming), "hipEventCreate");
+  ok = ok && hip_ok(s, hipEventCreateWithFlags(&s->slice_begin, hipEventDisableTiming), "hipEventCreate");
+  if (ok) P.pose = pose;          // (last: marks the set as complete)
   return ok;
 }
 static bool drain_tree_prepare(TreeHandle* s) {
   s->prep_pending = false;
-  return !s->prep_stream || t_ok(s, hipStreamSynchronize(s->prep_stream), "hipStreamSynchronize(prefetch)");
+  return !s->prep_stream || hip_ok(s, hipStreamSynchronize(s->prep_stream), "hipStreamSynchronize(prefetch)");
 }
 // k_tree_prepare behind whatever `stream` holds now, unless the previous launch is still running (it takes every env whose next episode is
 // missing, so a skipped launch only delays the refill)
@@ -765,30 +683,14 @@ int TAPI(create)(const void* blob, size_t bytes, int n_envs, int hip_device, Tre
   TreeHandle* s = new TreeHandle();
   s->n_envs = n_envs; s->device = hip_device;
   int rc = SO101_OK;
-  TreeDeviceGuard guard(s);                       // (the caller's current device is restored on every return path)
+  DeviceGuard guard(s);                       // (the caller's current device is restored on every return path)
   if (!guard.ok) rc = SO101_ERR_HIP;
   if (rc == SO101_OK) rc = tree_build(s, b);
-  if (rc == SO101_OK) {
-    void* p = nullptr;
-    if (!t_ok(s, hipMalloc(&p, (size_t)n_envs * T_SCRATCH * sizeof(float)), "hipMalloc(scratch)")) rc = SO101_ERR_HIP;
-    else { s->owned.push_back(p); s->buf.scratch = (float*)p; }
-  }
-  if (rc == SO101_OK) {
-    void* p = nullptr;
-    if (!t_ok(s, hipMalloc(&p, (size_t)n_envs * 8 * sizeof(int)), "hipMalloc(diag)")) rc = SO101_ERR_HIP;
-    else { s->owned.push_back(p); s->buf.diag = (int*)p; (void)hipMemset(p, 0, (size_t)n_envs * 8 * sizeof(int)); }
-  }
-  if (rc == SO101_OK) {
-    void* p = nullptr;
-    if (!t_ok(s, hipMalloc(&p, (size_t)n_envs), "hipMalloc(need_reset)")) rc = SO101_ERR_HIP;
-    else { s->owned.push_back(p); s->env.need_reset = (unsigned char*)p; (void)hipMemset(p, 1, (size_t)n_envs); }
-  }
-  if (rc == SO101_OK) {
-    void* p = nullptr;
-    if (!t_ok(s, hipMalloc(&p, (size_t)n_envs * sizeof(int)), "hipMalloc(success_state)")) rc = SO101_ERR_HIP;
-    else { s->owned.push_back(p); s->env.success_state = (int*)p; (void)hipMemset(p, 0, (size_t)n_envs * sizeof(int)); }
-  }
-  if (rc != SO101_OK) { g_tree_error = s->err; for (void* p : s->owned) (void)hipFree(p); delete s; return rc; }
+  size_t n = (size_t)n_envs;
+  if (rc == SO101_OK && !(dev_alloc(s, &s->buf.scratch, n * T_SCRATCH, -1, "hipMalloc(scratch)") && dev_alloc(s, &s->buf.diag, 8 * n, 0, "hipMalloc(diag)") &&
+                          dev_alloc(s, &s->env.need_reset, n, 1, "hipMalloc(need_reset)") && dev_alloc(s, &s->env.success_state, n, 0, "hipMalloc(success_state)")))
+    rc = SO101_ERR_HIP;
+  if (rc != SO101_OK) { g_tree_error = s->err; free_owned(s); delete s; return rc; }
   s->iterations = s->hm.iterations; s->tolerance = s->hm.tolerance;
   *out = s;
   return SO101_OK;
@@ -797,7 +699,7 @@ int TAPI(create)(const void* blob, size_t bytes, int n_envs, int hip_device, Tre
 void TAPI(destroy)(TreeHandle* s) {
   if (!s) return;
   {
-    TreeDeviceGuard guard(s);
+    DeviceGuard guard(s);
     (void)hipDeviceSynchronize();                 // nothing of this handle may still be running on buffers that are about to go
 #ifdef TREE_PROF
     {
@@ -818,7 +720,7 @@ void TAPI(destroy)(TreeHandle* s) {
     if (s->main_ev) (void)hipEventDestroy(s->main_ev);
     for (int g = 0; g < TreeHandle::MAXSLICES; g++) { if (s->slice_stream[g]) (void)hipStreamDestroy(s->slice_stream[g]); if (s->slice_done[g]) (void)hipEventDestroy(s->slice_done[g]); }
     if (s->slice_begin) (void)hipEventDestroy(s->slice_begin);
-    for (void* p : s->owned) (void)hipFree(p);
+    free_owned(s);
   }
   delete s;
 }
@@ -855,18 +757,18 @@ int TAPI(configure)(TreeHandle* s, int solver_iterations, float solver_tolerance
 int TAPI(physics)(TreeHandle* s, int n_substeps, void* stream) {
   if (!s || n_substeps < 0) return SO101_ERR_ARG;
   if (!s->bound) { s->err = "so101_tree_physics before so101_tree_bind_state"; return SO101_ERR_STATE; }
-  TREE_GUARD(s);
+  GUARD_DEVICE(s);
   hipLaunchKernelGGL(k_tree_physics, dim3(s->n_envs), dim3(64), 0, (hipStream_t)stream, s->dm, s->dg, s->buf, s->n_envs, n_substeps, s->iterations, s->tolerance);
-  return t_ok(s, hipGetLastError(), "k_tree_physics") ? SO101_OK : SO101_ERR_HIP;
+  return hip_ok(s, hipGetLastError(), "k_tree_physics") ? SO101_OK : SO101_ERR_HIP;
 }
 
 int TAPI(debug_forward)(TreeHandle* s, float* out, void* stream) {
   if (!s || !out) return SO101_ERR_ARG;
   if (!s->bound) { s->err = "so101_tree_debug_forward before so101_tree_bind_state"; return SO101_ERR_STATE; }
-  TREE_GUARD(s);
+  GUARD_DEVICE(s);
   static const int phases = getenv("SO101_TREE_PHASES") ? atoi(getenv("SO101_TREE_PHASES")) : 0x7f;      // timing runs only
   hipLaunchKernelGGL(k_tree_forward, dim3(s->n_envs), dim3(64), 0, (hipStream_t)stream, s->dm, s->dg, s->buf, s->n_envs, s->iterations, s->tolerance, out, phases);
-  return t_ok(s, hipGetLastError(), "k_tree_forward") ? SO101_OK : SO101_ERR_HIP;
+  return hip_ok(s, hipGetLastError(), "k_tree_forward") ? SO101_OK : SO101_ERR_HIP;
 }
 
 // ---- env layer (hand-over scenes)
@@ -904,13 +806,13 @@ int TAPI(configure_env)(TreeHandle* s, const so101_tree_config* c) {
   T.jdelay = jd; T.pdelay = pd;
   // reset prefetch: whatever the cache holds was settled under the previous configuration
   {
-    TREE_GUARD(s);
+    GUARD_DEVICE(s);
     if (!drain_tree_prepare(s)) return SO101_ERR_HIP;
     s->prefetch = c->prefetch_resets != 0;
     if (s->prefetch && !tree_prefetch_setup(s)) return SO101_ERR_HIP;
     s->pipeline = c->pipeline != 0;
     if (s->pipeline && !tree_pipe_setup(s)) return SO101_ERR_HIP;
-    if (s->ctag && !t_ok(s, hipMemset(s->ctag, 0, (size_t)s->n_envs * sizeof(unsigned int)), "hipMemset(prefetch)")) return SO101_ERR_HIP;
+    if (s->ctag && !hip_ok(s, hipMemset(s->ctag, 0, (size_t)s->n_envs * sizeof(unsigned int)), "hipMemset(prefetch)")) return SO101_ERR_HIP;
   }
   return TAPI(configure)(s, c->solver_iterations, c->solver_tolerance);
 }
@@ -919,9 +821,9 @@ int TAPI(configure_env)(TreeHandle* s, const so101_tree_config* c) {
 int TAPI(reset)(TreeHandle* s, const uint8_t* mask, void* stream) {
   if (!s) return SO101_ERR_ARG;
   if (!s->bound || !s->env_bound) { s->err = "so101_tree_reset before so101_tree_bind_state / so101_tree_bind_env"; return SO101_ERR_STATE; }
-  TREE_GUARD(s);
+  GUARD_DEVICE(s);
   hipLaunchKernelGGL(k_tree_reset, dim3(s->n_envs), dim3(64), 0, (hipStream_t)stream, s->dm, s->dg, task_now(s), s->buf, s->env, store_now(s), mask);
-  if (!t_ok(s, hipGetLastError(), "k_tree_reset")) return SO101_ERR_HIP;
+  if (!hip_ok(s, hipGetLastError(), "k_tree_reset")) return SO101_ERR_HIP;
   launch_tree_prepare(s, (hipStream_t)stream);
   return SO101_OK;
 }
@@ -929,7 +831,7 @@ int TAPI(reset)(TreeHandle* s, const uint8_t* mask, void* stream) {
 int TAPI(step)(TreeHandle* s, const float* action, float* obs, float* reward, float* discount, uint8_t* step_type, void* stream) {
   if (!s || !action || !obs || !reward || !discount || !step_type) { if (s) s->err = "so101_tree_step: NULL argument"; return SO101_ERR_ARG; }
   if (!s->bound || !s->env_bound) { s->err = "so101_tree_step before so101_tree_bind_state / so101_tree_bind_env"; return SO101_ERR_STATE; }
-  TREE_GUARD(s);
+  GUARD_DEVICE(s);
   hipStream_t st = (hipStream_t)stream;
   TreeTask T = task_now(s);
   const bool post = T.reward_mode != 0;          // contact rewards: one more narrowphase launch, on the post-step state
@@ -940,7 +842,7 @@ int TAPI(step)(TreeHandle* s, const float* action, float* obs, float* reward, fl
     // ALOHA (4096 envs) 206 / 232 / 228 / 231 k, Dining (1024 envs) 33.2 / 44.6 / - / 47.0 k env-steps/s.
     static const int slices_env = getenv("SO101_TREE_SLICES") ? atoi(getenv("SO101_TREE_SLICES")) : 0;          // (kernel experiments)
     const int G = s->n_envs < 128 ? 1 : (slices_env >= 1 && slices_env <= TreeHandle::MAXSLICES ? slices_env : (s->n_envs < 512 ? 2 : 4));
-    if (G > 1 && !t_ok(s, hipEventRecord(s->slice_begin, st), "hipEventRecord")) return SO101_ERR_HIP;
+    if (G > 1 && !hip_ok(s, hipEventRecord(s->slice_begin, st), "hipEventRecord")) return SO101_ERR_HIP;
     s->plan[0] = G; s->plan[1] = G * (1 + 2 * T.n_substeps + (post ? 2 : 0)); s->plan[2] = G; s->plan[3] = 2;
     for (int g = 0; g < G; g++) {
       int e0 = (int)((long long)s->n_envs * g / G), ng = (int)((long long)s->n_envs * (g + 1) / G) - e0;
@@ -951,8 +853,8 @@ int TAPI(step)(TreeHandle* s, const float* action, float* obs, float* reward, fl
       P.work_cap = (unsigned int)ng * TCAND;
       static const int nwq_env = getenv("SO101_TREE_NARROW_WAVES_Q") ? atoi(getenv("SO101_TREE_NARROW_WAVES_Q")) : 0;      // (kernel experiments: quarter waves per env)
       int nw = (int)((long long)ng * (nwq_env > 0 ? nwq_env : 8) / 4); nw = nw < 1 ? 1 : (nw < 4096 ? nw : 4096);
-      if (G > 1 && !t_ok(s, hipStreamWaitEvent(gs, s->slice_begin, 0), "hipStreamWaitEvent")) return SO101_ERR_HIP;
-      if (!t_ok(s, hipMemsetAsync(P.counters, 0, 2 * TPIPE_MAXSUB * sizeof(int), gs), "hipMemsetAsync(pipeline)")) return SO101_ERR_HIP;
+      if (G > 1 && !hip_ok(s, hipStreamWaitEvent(gs, s->slice_begin, 0), "hipStreamWaitEvent")) return SO101_ERR_HIP;
+      if (!hip_ok(s, hipMemsetAsync(P.counters, 0, 2 * TPIPE_MAXSUB * sizeof(int), gs), "hipMemsetAsync(pipeline)")) return SO101_ERR_HIP;
       hipLaunchKernelGGL(k_tree_pipe_begin, dim3(ng), dim3(64), 0, gs, s->dm, s->dg, T, s->buf, s->env, store_now(s), P, action, obs, reward, discount, step_type, e0);
       for (int k = 0; k < T.n_substeps; k++) {
         hipLaunchKernelGGL(k_tree_narrow, dim3(nw), dim3(64), 0, gs, s->dm, s->dg, P, s->n_envs, k);
@@ -962,13 +864,13 @@ int TAPI(step)(TreeHandle* s, const float* action, float* obs, float* reward, fl
         hipLaunchKernelGGL(k_tree_narrow, dim3(nw), dim3(64), 0, gs, s->dm, s->dg, P, s->n_envs, T.n_substeps);
         hipLaunchKernelGGL(k_tree_pipe_finish, dim3(ng), dim3(64), 0, gs, s->dm, s->dg, T, s->buf, s->env, P, obs, reward, discount, step_type, e0);
       }
-      if (!t_ok(s, hipGetLastError(), "k_tree_pipe_solve")) return SO101_ERR_HIP;
-      if (G > 1 && !(t_ok(s, hipEventRecord(s->slice_done[g], gs), "hipEventRecord") && t_ok(s, hipStreamWaitEvent(st, s->slice_done[g], 0), "hipStreamWaitEvent"))) return SO101_ERR_HIP;
+      if (!hip_ok(s, hipGetLastError(), "k_tree_pipe_solve")) return SO101_ERR_HIP;
+      if (G > 1 && !(hip_ok(s, hipEventRecord(s->slice_done[g], gs), "hipEventRecord") && hip_ok(s, hipStreamWaitEvent(st, s->slice_done[g], 0), "hipStreamWaitEvent"))) return SO101_ERR_HIP;
     }
   } else {
     s->plan[0] = 1; s->plan[1] = 1; s->plan[2] = 0; s->plan[3] = 1;
     hipLaunchKernelGGL(k_tree_step, dim3(s->n_envs), dim3(64), 0, st, s->dm, s->dg, T, s->buf, s->env, store_now(s), action, obs, reward, discount, step_type);
-    if (!t_ok(s, hipGetLastError(), "k_tree_step")) return SO101_ERR_HIP;
+    if (!hip_ok(s, hipGetLastError(), "k_tree_step")) return SO101_ERR_HIP;
   }
   launch_tree_prepare(s, (hipStream_t)stream);
   return SO101_OK;
@@ -977,11 +879,11 @@ int TAPI(step)(TreeHandle* s, const float* action, float* obs, float* reward, fl
 int TAPI(compute_settled)(TreeHandle* s, int first_episode, int count, float* qpos, float* qvel, float* warmstart, int32_t* flags, void* stream) {
   if (!s || !qpos || !qvel || !warmstart || !flags || first_episode < 0 || count <= 0) { if (s) s->err = "so101_tree_compute_settled: bad argument"; return SO101_ERR_ARG; }
   if (!s->has_task) { s->err = "so101_tree_compute_settled: the model carries no task"; return SO101_ERR_STATE; }
-  TREE_GUARD(s);
+  GUARD_DEVICE(s);
   for (int k = 0; k < count; k++) {      // one launch per episode: the per-env scratch is used by one wavefront at a time
     hipLaunchKernelGGL(k_tree_settle_table, dim3(s->n_envs), dim3(64), 0, (hipStream_t)stream, s->dm, s->dg, task_now(s), s->buf, (unsigned int)(first_episode + k), k,
                        qpos, qvel, warmstart, flags);
-    if (!t_ok(s, hipGetLastError(), "k_tree_settle_table")) return SO101_ERR_HIP;
+    if (!hip_ok(s, hipGetLastError(), "k_tree_settle_table")) return SO101_ERR_HIP;
   }
   return SO101_OK;
 }
@@ -997,23 +899,23 @@ int TAPI(set_settled_store)(TreeHandle* s, int first_episode, int count, const f
 int TAPI(settle)(TreeHandle* s, void* stream) {
   if (!s) return SO101_ERR_ARG;
   if (!s->bound) { s->err = "so101_tree_settle before so101_tree_bind_state"; return SO101_ERR_STATE; }
-  TREE_GUARD(s);
+  GUARD_DEVICE(s);
   hipLaunchKernelGGL(k_tree_settle, dim3(s->n_envs), dim3(64), 0, (hipStream_t)stream, s->dm, s->dg, task_now(s), s->buf);
-  return t_ok(s, hipGetLastError(), "k_tree_settle") ? SO101_OK : SO101_ERR_HIP;
+  return hip_ok(s, hipGetLastError(), "k_tree_settle") ? SO101_OK : SO101_ERR_HIP;
 }
 
 int TAPI(begin_episode)(TreeHandle* s, void* stream) {
   if (!s) return SO101_ERR_ARG;
   if (!s->bound || !s->env_bound) { s->err = "so101_tree_begin_episode before so101_tree_bind_state / so101_tree_bind_env"; return SO101_ERR_STATE; }
-  TREE_GUARD(s);
+  GUARD_DEVICE(s);
   hipLaunchKernelGGL(k_tree_begin, dim3(s->n_envs), dim3(64), 0, (hipStream_t)stream, s->dm, task_now(s), s->buf, s->env);
-  return t_ok(s, hipGetLastError(), "k_tree_begin") ? SO101_OK : SO101_ERR_HIP;
+  return hip_ok(s, hipGetLastError(), "k_tree_begin") ? SO101_OK : SO101_ERR_HIP;
 }
 
 int TAPI(get_diag)(TreeHandle* s, int* out /* [n_envs][8] device or host-visible memory */, void* stream) {
   if (!s || !out) return SO101_ERR_ARG;
-  TREE_GUARD(s);
-  return t_ok(s, hipMemcpyAsync(out, s->buf.diag, (size_t)s->n_envs * 8 * sizeof(int), hipMemcpyDefault, (hipStream_t)stream), "hipMemcpyAsync(diag)") ? SO101_OK : SO101_ERR_HIP;
+  GUARD_DEVICE(s);
+  return hip_ok(s, hipMemcpyAsync(out, s->buf.diag, (size_t)s->n_envs * 8 * sizeof(int), hipMemcpyDefault, (hipStream_t)stream), "hipMemcpyAsync(diag)") ? SO101_OK : SO101_ERR_HIP;
 }
 
 }  // extern "C"

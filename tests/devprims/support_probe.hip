@@ -1,4 +1,4 @@
-// TEST HARNESS ONLY - device probes of the hull support queries of so101_device.hpp, for tests/test_support_queries.py.
+// TEST HARNESS ONLY - device probes of the hull support queries of so101_geom.hpp, for tests/test_support_queries.py.
 // tests/devprims/__init__.py builds this file with hipcc for gfx950 (the product's flags, so101_sim_amd/build.py FLAGS) or with g++ against the
 // lane-thread emulation of tests/hostemu.  The product never links it (so101_sim_amd/build.py compiles csrc/*.hip only).
 // One hull per handle: a mesh geom at the origin with the identity rotation, so that a support point is a vertex, float for float.  Support
@@ -9,7 +9,7 @@ thread_local emu_idx threadIdx;
 thread_local emu_idx blockIdx;
 thread_local EmuBlock* emu_blk;
 #endif
-#include "../../so101_sim_amd/csrc/so101_device.hpp"
+#include "../../so101_sim_amd/csrc/so101_geom.hpp"
 #include "../../so101_sim_amd/csrc/so101_tables.hpp"
 
 #include <cmath>

@@ -20,7 +20,7 @@ NQ, NV, NU = 20, 18, 6
 
 
 def build_emu(mpr: bool = False):
-    """mpr: the -DSO101_MPR build of the kernel source (MPR's own portal depth instead of the EPA expansion, so101_device.hpp)"""
+    """mpr: the -DSO101_MPR build of the kernel source (MPR's own portal depth instead of the EPA expansion, so101_geom.hpp)"""
     subprocess.check_call(["make", "-C", os.path.join(_HERE, "hostemu"), "-s"] + (["mpr"] if mpr else []))
     return EMU_LIB.replace("libso101_emu.so", "libso101_emu_mpr.so") if mpr else EMU_LIB
 

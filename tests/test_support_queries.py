@@ -1,7 +1,7 @@
 """Hull support queries and the per-hull tables built on them, against an fp64 brute force.
 
 The support point of a hull in a direction is the vertex with the largest dot product, the smallest index winning ties.  The device
-functions of so101_device.hpp run in the probe kernels of tests/devprims (one query per 64-lane workgroup, the hull at the origin with the
+functions of so101_geom.hpp run in the probe kernels of tests/devprims (one query per 64-lane workgroup, the hull at the origin with the
 identity rotation, so a support point is a vertex float for float); the tables come from so101_tables.hpp, the builder both engines call.
   paths agree       every support() / support_patch() path (NoCache, HullCache, HullLDS with 256 / 512 / 0 slots, HullLDS under G16, HullSub)
                     returns the NoCache point bit for bit
@@ -142,7 +142,7 @@ def patch_frames(dirs):
 
 
 def patch_dirs64(frames):
-    """the NCPP directions support_patch() queries, in fp64 (so101_device.hpp support_patch)"""
+    """the NCPP directions support_patch() queries, in fp64 (so101_geom.hpp support_patch)"""
     fr = frames.astype(F64)
     f, u, v = fr[:, 0:3], fr[:, 3:6], fr[:, 6:9]
     out = []
