@@ -33,7 +33,8 @@
 extern "C" {
 #endif
 
-#define SO101_ABI_VERSION 10     /* 10: so101_tree_last_plan; 9: so101_tree_config gains the observation delays, so101_tree_bind_physics_state; 8: the general-tree engine (so101_tree_*) */
+#define SO101_ABI_VERSION 10     /* 10: so101_tree_last_plan, and (additions that change nothing older, so the number stays) the cameras: so101_camera,
+                                    so101_set_hull_planes, so101_render; 9: so101_tree_config gains the observation delays, so101_tree_bind_physics_state; 8: the general-tree engine (so101_tree_*) */
 #define SO101_OBS_DIM 18      /* joints_pos(6, delayed) | undelayed_joints_pos(6) | commanded_joints_pos(6) */
 #define SO101_ACT_DIM 6
 #define SO101_SOLVER_PGS 0
@@ -251,6 +252,31 @@ long long so101_get_info(so101_sim* sim, int what, void* hip_stream);
  * [2] narrowphase chunks, [3] solve items (10 ns ticks, summed over wavefronts); [4] chunks, [5] solve items, [6] idle
  * rounds, [7] wavefronts that ran, [8] their lifetimes (ticks). */
 int so101_debug_chain_stats(so101_sim* sim, uint64_t* out, int clear, void* hip_stream);
+
+/* ---- depth and segmentation cameras: batched ray casting against the COLLISION geometry the step sees (csrc/so101_camera.hpp).  Stands in for
+ * the depth / segmentation renders of physics.render(camera_id=..., depth=True | segmentation=True) on the reference's cameras
+ * (so100_task.py:107-112, scene_pbr.xml:70-71,113,138-139); RGB, textures and visual-only meshes are not rendered.
+ *
+ * so101_set_hull_planes: the facet planes of the mesh geoms' convex hulls, geom frame: planes[n][4] = unit outward normal n and offset d with
+ * n . x + d <= 0 inside; plane_adr[ngeom + 1] = each geom's range (HOST arrays, copied; so101_sim_amd.model.meshes.hull_planes computes them).
+ * Checked before the upload - SO101_ERR_ARG with a message naming the geom: non-mesh geoms have empty ranges, a mesh geom has at least 4 planes,
+ * | |n| - 1 | <= 1e-4, every vertex of the hull has n . v + d <= 1e-5, every plane has a vertex within 1e-5 of it. */
+int so101_set_hull_planes(so101_sim* sim, const float* planes, const int32_t* plane_adr);
+typedef struct {
+  int32_t body;       /* -1 world, 0..5 arm link, 6..7 free prop (the numbering of the model's geom_dyn) */
+  float pos[3];       /* camera frame in that body's frame */
+  float mat[9];       /* row-major, columns x (right), y (up), z; the camera looks along -z (MuJoCo's convention) */
+  float fovy_deg;     /* vertical field of view, 0 < fovy_deg < 180 */
+} so101_camera;
+/* Renders ncam cameras (HOST array, 1..8) at height x width (1..4096 each) for n_render envs from the qpos in the bound buffers; asynchronous on
+ * `hip_stream`, changes no state.  env_index: DEVICE array of n_render env indices, or NULL for envs 0 .. n_render - 1 (n_render = n_envs: all).
+ * depth / seg: DEVICE arrays [n_render][ncam][height][width], either may be NULL.  Pixel (r, c): the ray from the camera position along the
+ * camera-frame direction ((c + 0.5 - W/2) s, -(r + 0.5 - H/2) s, -1), s = 2 tan(fovy / 2) / H; depth = the ray parameter of the nearest hit (the
+ * distance along the optical axis), +inf without one; seg = the geom index, -1 without one; equal depths: the lower index.  A plane is hit from its
+ * front only and clipped to its positive sizes, a geom that contains the camera position is invisible.  A pixel's bits depend on the env's qpos,
+ * the camera and (r, c, height, width) only.  SO101_ERR_STATE while the scene has mesh geoms and so101_set_hull_planes has not been called. */
+int so101_render(so101_sim* sim, const so101_camera* cams, int ncam, int height, int width, const int32_t* env_index, int n_render,
+                 float* depth, int32_t* seg, void* hip_stream);
 
 const char* so101_last_error(const so101_sim* sim);
 

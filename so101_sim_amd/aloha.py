@@ -8,7 +8,7 @@ Every number comes from the kernels behind the `so101_tree_*` entry points of in
 array container.  n_envs == 1 yields numpy observations without the env dimension (what a caller of the reference sees), n_envs > 1
 torch tensors on the GPU with a leading env dimension.
 
-Not built: cameras (no renderer in this library) and a non-default table height offset (the committed model blob is compiled for
+Not built: cameras (the depth / segmentation ray caster, so101_render, serves the SO100 engine only) and a non-default table height offset (the committed model blob is compiled for
 the reference's default).  The observation delays ARE parameters (`joints_observation_delay_secs`, `image_observation_delay_secs`,
 aloha2_task.py:153-159: whole control steps, handed to the kernels by so101_tree_configure_env), and `physics_state` /
 `delayed_physics_state` come from a device-side delay line (so101_tree_bind_physics_state).  Both reward modes are built: the overlap boxes (default) and the contact sequence

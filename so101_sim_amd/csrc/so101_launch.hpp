@@ -26,6 +26,11 @@ void launch_debug_forward(int solver, int n_envs, hipStream_t st, const DevModel
 void launch_begin(int n_envs, hipStream_t st, const DevModel* m, const StepParams& P, const DevBuffers& B, unsigned char* need_reset);
 void launch_reward(int n_envs, hipStream_t st, const DevModel* m, const StepParams& P, const DevBuffers& B, float* reward);
 
+// depth / segmentation cameras (so101_camera.hpp): frames of n_render envs, then one wavefront per 8 x 8 tile of every (env, camera) image
+void launch_render(int n_render, hipStream_t st, const DevModel* m, const StepParams& P, const DevBuffers& B, const int* env_index, const RenderCams& cams,
+                   int ncam, int height, int width, const float* planes, const int* plane_adr, float* frames, float* camframes,
+                   float* depth, int* seg);
+
 // pipelined step (Newton) -----------------------------------------------------------------------------------------
 void launch_order(hipStream_t st, const unsigned int* cost, int* order, unsigned char* cls, int n_envs, int deal = 1);   // deal: equal slices the sorted envs are dealt to (1 = plain sorted order)
 void launch_pipe_begin(int n_group, hipStream_t st, const DevModel* m, const StepParams& P, const DevBuffers& B, const PrepBuffers& C,

@@ -332,6 +332,47 @@ class BatchedEnvironment:
         self.set_settled_store(tuple(arrays[a[0]] for a in settled_cache.ARRAYS), header["first_episode"])
         return header
 
+    # ------------------------------------------------------------------ depth / segmentation cameras (cameras.py)
+    def _ensure_hull_planes(self):
+        """Facet planes of the mesh geoms' hulls, computed from the blob's vertices and handed to the library on first use"""
+        if getattr(self, "_planes_set", False):
+            return
+        from .model import blob as blobfmt, meshes
+        m = blobfmt.unpack(scenes.load_blob(self.task.object_name, "f32")[0])
+        verts = np.asarray(m["mesh_vert"], dtype=np.float64).reshape(-1, 3)
+        adr, chunks = [0], []
+        for t, a, n in zip(m["geom_type"], m["geom_vertadr"], m["geom_vertnum"]):
+            if int(t) == 5:
+                chunks.append(meshes.hull_planes(verts[a:a + n]))
+            adr.append(adr[-1] + (len(chunks[-1]) if int(t) == 5 else 0))
+        planes = np.concatenate(chunks) if chunks else np.zeros((0, 4))
+        self.sim.set_hull_planes(planes.astype(np.float32), np.asarray(adr, dtype=np.int32))
+        self._planes_set = True
+
+    def render_depth(self, camera, height: int, width: int, env_ids=None, segmentation: bool = True):
+        """Depth and geom-id images of the collision geometry at the current state, by ray casting on the GPU (so101_render).
+
+        camera: a name of cameras.SO100_CAMERAS, a cameras.Camera, or a sequence of either (at most 8).
+        env_ids: env indices to render (sequence or tensor), None = all.
+        Returns (depth [n, ncam, height, width] float32, seg int32 of the same shape or None) on the env's device.  depth is the
+        distance along the optical axis, +inf where the ray hits nothing; seg the geom index (`meta["geom_names"][i]` names it),
+        -1 where it hits nothing.  This is not RGB: textures and visual-only meshes are not rendered."""
+        from . import cameras as _cameras
+        torch = self.torch
+        cams = _cameras.resolve(camera)
+        self._ensure_hull_planes()
+        idx, n = None, self.n_envs
+        if env_ids is not None:
+            idx = torch.as_tensor(env_ids, dtype=torch.int32, device=self.device).reshape(-1).contiguous()
+            n = int(idx.numel())
+            if n == 0 or int(idx.min()) < 0 or int(idx.max()) >= self.n_envs:
+                raise ValueError("env_ids must name at least one env of this batch")
+        depth = torch.empty(n, len(cams), int(height), int(width), dtype=torch.float32, device=self.device)
+        seg = torch.empty(n, len(cams), int(height), int(width), dtype=torch.int32, device=self.device) if segmentation else None
+        self.sim.render([c.spec() for c in cams], height, width, idx.data_ptr() if idx is not None else None, n,
+                        depth.data_ptr(), seg.data_ptr() if seg is not None else None, self._stream())
+        return depth, seg
+
     def events(self, clear: bool = False) -> dict:
         """Counts since creation (or the last clear) of env-steps / env-resets that raised a flag: contact or candidate
         overflow, physics divergence (episode ended like a dm_control PhysicsError), rejected placement, unsettled

@@ -73,6 +73,15 @@ def convex_hull(verts: np.ndarray) -> tuple[np.ndarray, np.ndarray]:
     return hv, tris
 
 
+def hull_planes(verts: np.ndarray) -> np.ndarray:
+    """Facet planes [F, 4] (float64) of the convex hull of `verts`: unit outward normal n and offset d per row, n . x + d <= 0 inside.
+    The triangles qhull cuts one flat facet into carry the same equation; those rows are merged (the polytope is the same with or
+    without them: the depth cameras of so101_render intersect rays with these half-spaces)."""
+    eq = ConvexHull(np.asarray(verts, dtype=np.float64)).equations
+    eq = eq / np.linalg.norm(eq[:, :3], axis=1, keepdims=True)
+    return np.unique(eq, axis=0)
+
+
 def polyhedron_mass_properties(verts: np.ndarray, faces: np.ndarray):
     """Volume, centre of mass and inertia tensor about the COM (unit density) of a closed,
     outward-oriented triangle mesh, by signed tetrahedra against the origin."""

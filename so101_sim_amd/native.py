@@ -32,6 +32,7 @@ EXPORTS = (
     "so101_version", "so101_max_contacts", "so101_create", "so101_destroy", "so101_default_config",
     "so101_configure", "so101_bind_state", "so101_bind_physics_state", "so101_set_reset_pool", "so101_compute_settled", "so101_set_settled_store", "so101_reset", "so101_settle", "so101_begin_episode", "so101_step", "so101_physics", "so101_reward",
     "so101_get_returns", "so101_get_diag", "so101_get_events", "so101_debug_forward", "so101_debug_candidates", "so101_debug_stages", "so101_get_info", "so101_debug_chain_stats", "so101_last_error",
+    "so101_set_hull_planes", "so101_render",
     "so101_tree_create", "so101_tree_destroy", "so101_tree_dims", "so101_tree_last_plan", "so101_tree_bind_state", "so101_tree_configure", "so101_tree_physics",
     "so101_tree_debug_forward", "so101_tree_get_diag", "so101_tree_last_error", "so101_tree_obs_dim", "so101_tree_bind_env",
     "so101_tree_configure_env", "so101_tree_bind_physics_state", "so101_tree_reset", "so101_tree_step", "so101_tree_begin_episode", "so101_tree_settle", "so101_tree_compute_settled", "so101_tree_set_settled_store",
@@ -50,6 +51,11 @@ class Config(C.Structure):
                 ("settle_max_substeps", C.c_int32), ("terminate_on_success", C.c_int32),
                 ("env_id_base", C.c_uint64), ("solver", C.c_int32), ("prefetch_resets", C.c_int32), ("pipeline", C.c_int32),
                 ("groups", C.c_int32), ("use_graph", C.c_int32), ("chain_waves", C.c_int32)]
+
+
+class CameraSpec(C.Structure):
+    """so101_camera of include/so101.h"""
+    _fields_ = [("body", C.c_int32), ("pos", C.c_float * 3), ("mat", C.c_float * 9), ("fovy_deg", C.c_float)]
 
 
 _libs: dict[str, C.CDLL] = {}
@@ -100,6 +106,8 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.so101_get_info.argtypes = [vp, C.c_int, vp]
     L.so101_last_error.restype = C.c_char_p
     L.so101_last_error.argtypes = [vp]
+    L.so101_set_hull_planes.argtypes = [vp, vp, vp]
+    L.so101_render.argtypes = [vp, C.POINTER(CameraSpec), C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp]
     _libs[path] = L
     return L
 
@@ -217,6 +225,23 @@ class Sim:
 
     def debug_forward(self, out, stream=0):
         self._check(self.L.so101_debug_forward(self.h, out, stream), "so101_debug_forward")
+
+    def set_hull_planes(self, planes, plane_adr):
+        """planes [n, 4] float32 and plane_adr [ngeom + 1] int32: HOST numpy arrays (so101_set_hull_planes copies them)"""
+        import numpy as np
+        planes = np.ascontiguousarray(planes, dtype=np.float32).reshape(-1, 4)
+        plane_adr = np.ascontiguousarray(plane_adr, dtype=np.int32)
+        self._check(self.L.so101_set_hull_planes(self.h, planes.ctypes.data, plane_adr.ctypes.data), "so101_set_hull_planes")
+
+    def render(self, cams, height: int, width: int, env_index, n_render: int, depth, seg, stream=0):
+        """cams: sequence of (body, pos[3], mat[9] row-major, fovy_deg); env_index / depth / seg: raw device addresses or None"""
+        arr = (CameraSpec * max(len(cams), 1))()
+        for k, (body, pos, mat, fovy) in enumerate(cams):
+            arr[k].body = int(body)
+            arr[k].pos[:] = [float(x) for x in pos]
+            arr[k].mat[:] = [float(x) for x in mat]
+            arr[k].fovy_deg = float(fovy)
+        self._check(self.L.so101_render(self.h, arr, len(cams), int(height), int(width), env_index, int(n_render), depth, seg, stream), "so101_render")
 
 
 class TreeConfig(C.Structure):
