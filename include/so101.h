@@ -34,7 +34,7 @@ extern "C" {
 #endif
 
 #define SO101_ABI_VERSION 10     /* 10: so101_tree_last_plan, and (additions that change nothing older, so the number stays) the cameras: so101_camera,
-                                    so101_set_hull_planes, so101_render; 9: so101_tree_config gains the observation delays, so101_tree_bind_physics_state; 8: the general-tree engine (so101_tree_*) */
+                                    so101_set_hull_planes, so101_render, so101_tree_set_hull_planes, so101_tree_render; 9: so101_tree_config gains the observation delays, so101_tree_bind_physics_state; 8: the general-tree engine (so101_tree_*) */
 #define SO101_OBS_DIM 18      /* joints_pos(6, delayed) | undelayed_joints_pos(6) | commanded_joints_pos(6) */
 #define SO101_ACT_DIM 6
 #define SO101_SOLVER_PGS 0
@@ -263,7 +263,8 @@ int so101_debug_chain_stats(so101_sim* sim, uint64_t* out, int clear, void* hip_
  * | |n| - 1 | <= 1e-4, every vertex of the hull has n . v + d <= 1e-5, every plane has a vertex within 1e-5 of it. */
 int so101_set_hull_planes(so101_sim* sim, const float* planes, const int32_t* plane_adr);
 typedef struct {
-  int32_t body;       /* -1 world, 0..5 arm link, 6..7 free prop (the numbering of the model's geom_dyn) */
+  int32_t body;       /* so101_render: -1 world, 0..5 arm link, 6..7 free prop (the numbering of the model's geom_dyn); so101_tree_render: -1 or 0
+                         world, 1 .. nbody - 1 a body of the tree (the blob's body numbering) */
   float pos[3];       /* camera frame in that body's frame */
   float mat[9];       /* row-major, columns x (right), y (up), z; the camera looks along -z (MuJoCo's convention) */
   float fovy_deg;     /* vertical field of view, 0 < fovy_deg < 180 */
@@ -367,6 +368,20 @@ int so101_tree_settle(so101_tree* sim, void* hip_stream);
 int so101_tree_begin_episode(so101_tree* sim, void* hip_stream);
 int so101_tree_step(so101_tree* sim, const float* action /*[n_envs][nu]*/, float* obs, float* reward, float* discount, uint8_t* step_type,
                     void* hip_stream);
+/* ---- depth and segmentation cameras of this engine: so101_set_hull_planes / so101_render above, word for word, on a tree handle - the same
+ * image kernel fed by this engine's kinematics.  Stands in for the depth / segmentation renders of the cameras the reference turns on for these
+ * tasks (aloha2_task.py:151-232 cameras=('overhead_cam',), scene_pbr.xml:74-77, aloha_pbr.xml:122-123,172,256); RGB is not rendered.
+ *
+ * so101_tree_set_hull_planes: same arrays, same checks, same error messages (naming the geom) as so101_set_hull_planes.
+ * so101_tree_render: a camera's `body` is a tree body id (-1 or 0: fixed to the world).  source selects the qpos the kinematics runs on:
+ * 0 = the bound state (so101_tree_bind_state), 1 = the `delayed` buffer of so101_tree_bind_physics_state (its first nq entries per env: what the
+ * reference's delayed camera observables look at).  Pixel definition, argument limits, tie rule and "a pixel's bits depend on that env's qpos,
+ * the camera and (r, c, height, width) only" are those of so101_render; asynchronous on `hip_stream`, changes no state.  SO101_ERR_STATE while
+ * the scene has mesh geoms and so101_tree_set_hull_planes has not been called, and for source 1 without a bound physics-state line;
+ * SO101_ERR_ARG for a body outside -1 .. nbody - 1, a bad fovy_deg or another source. */
+int so101_tree_set_hull_planes(so101_tree* sim, const float* planes, const int32_t* plane_adr);
+int so101_tree_render(so101_tree* sim, const so101_camera* cams, int ncam, int height, int width, const int32_t* env_index, int n_render,
+                      int source, float* depth, int32_t* seg, void* hip_stream);
 const char* so101_tree_last_error(const so101_tree* sim);
 
 #ifdef __cplusplus

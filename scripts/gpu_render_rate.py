@@ -1,11 +1,14 @@
-"""Rate of the depth / segmentation cameras (so101_render) on the MI355X, beside the control step of the same envs.
+"""Rate of the depth / segmentation cameras (so101_render / so101_tree_render) on the MI355X, beside the control step of the same envs.
 
-    python scripts/gpu_render_rate.py [--envs 4096] [--sizes 64 128] [--out FILE]
+    python scripts/gpu_render_rate.py [--workload so100|aloha|dining] [--envs N] [--sizes 64 128] [--out FILE]
 
 Per image size one child process under `timeout` (the run stops at the first one that fails): 4096 SO100HandOverBanana envs, reset, 100
 control steps of the headline workload (uniform random actions, bench.py's), then overhead_cam + front_cam of every env: two warm-up calls,
 ten timed ones between device events.  Prints one JSON line per size: ms per so101_render call, images per second, and the control-step
 time of the same envs over 20 steps right before (the stepping kernels are the parent commit's: no stepping code differs).
+
+--workload aloha: 4096 HandOverBanana envs of the general-tree engine, bench.py's actions of that workload (uniform around the home pose),
+overhead_cam + wrist_cam_left; --workload dining: 1024 DiningPlaceBananaInBowl envs, the same cameras.  The default (so100) is the run above.
 """
 import argparse
 import json
@@ -15,19 +18,33 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CAMS = ("overhead_cam", "front_cam")
+WORKLOADS = {          # task, default envs, cameras
+    "so100": ("SO100HandOverBanana", 4096, CAMS),
+    "aloha": ("HandOverBanana", 4096, ("overhead_cam", "wrist_cam_left")),
+    "dining": ("DiningPlaceBananaInBowl", 1024, ("overhead_cam", "wrist_cam_left")),
+}
 
 
-def child(n_envs, size):
+def child(n_envs, size, workload="so100"):
     sys.path.insert(0, ROOT)
     import torch
     from so101_sim_amd import task_suite
     assert torch.cuda.is_available(), "this measurement needs the MI355X"
-    env = task_suite.create_task_env("SO100HandOverBanana", time_limit=10.0, random_state=0, n_envs=n_envs)
+    task, _, CAMS = WORKLOADS[workload]
+    env = task_suite.create_task_env(task, time_limit=10.0, random_state=0, n_envs=n_envs)
     spec = env.action_spec()
     lo, hi = (torch.tensor(a, device=env.device) for a in (spec.minimum, spec.maximum))
     gen = torch.Generator(device=env.device).manual_seed(0)
-    tape = lo + (hi - lo) * torch.rand(120, n_envs, 6, device=env.device, generator=gen)
-    env.reset_all()
+    if workload == "so100":
+        tape = lo + (hi - lo) * torch.rand(120, n_envs, 6, device=env.device, generator=gen)
+        env.reset_all()
+    else:
+        import numpy as np
+        from so101_sim_amd.model import scenes
+        home = torch.tensor(np.concatenate([scenes.ALOHA_HOME_CTRL] * 2), dtype=torch.float32, device=env.device)
+        tape = torch.clamp(home + 0.5 * (torch.rand(120, n_envs, 14, device=env.device, generator=gen) - 0.5), lo, hi)
+        env.reset()
+        env.render_depth(CAMS, 8, 8)          # (the hull planes are computed and uploaded here, outside everything timed)
     for i in range(100):
         env.step_tensor(tape[i])
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
@@ -44,23 +61,25 @@ def child(n_envs, size):
     torch.cuda.synchronize()
     step_ms, render_ms = ev[0].elapsed_time(ev[1]) / 20, ev[2].elapsed_time(ev[3]) / 10
     hit = float(torch.isfinite(depth).float().mean())
-    print(json.dumps(dict(envs=n_envs, cameras=list(CAMS), height=size, width=size, render_ms_per_call=round(render_ms, 3),
+    print(json.dumps(dict(**({} if workload == "so100" else {"workload": workload}), envs=n_envs, cameras=list(CAMS), height=size, width=size, render_ms_per_call=round(render_ms, 3),
                           images_per_s=round(n_envs * len(CAMS) / (render_ms * 1e-3)), pixels_per_s=round(n_envs * len(CAMS) * size * size / (render_ms * 1e-3)),
                           control_step_ms=round(step_ms, 3), render_over_step=round(render_ms / step_ms, 3), hit_fraction=round(hit, 3))), flush=True)
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--envs", type=int, default=4096)
+    ap.add_argument("--workload", choices=sorted(WORKLOADS), default="so100")
+    ap.add_argument("--envs", type=int, default=0, help="0: the workload's default (4096; dining 1024)")
     ap.add_argument("--sizes", type=int, nargs="+", default=[64, 128])
     ap.add_argument("--out", default="")
     ap.add_argument("--child", type=int, default=0)
     args = ap.parse_args()
+    args.envs = args.envs or WORKLOADS[args.workload][1]
     if args.child:
-        return child(args.envs, args.child)
+        return child(args.envs, args.child, args.workload)
     lines = []
     for size in args.sizes:
-        r = subprocess.run(["timeout", "-k", "10", "240", sys.executable, os.path.abspath(__file__), "--envs", str(args.envs), "--child", str(size)],
+        r = subprocess.run(["timeout", "-k", "10", "300", sys.executable, os.path.abspath(__file__), "--workload", args.workload, "--envs", str(args.envs), "--child", str(size)],
                            stdout=subprocess.PIPE, text=True)
         sys.stdout.write(r.stdout)
         if r.returncode != 0:

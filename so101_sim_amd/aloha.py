@@ -8,8 +8,9 @@ Every number comes from the kernels behind the `so101_tree_*` entry points of in
 array container.  n_envs == 1 yields numpy observations without the env dimension (what a caller of the reference sees), n_envs > 1
 torch tensors on the GPU with a leading env dimension.
 
-Not built: cameras (the depth / segmentation ray caster, so101_render, serves the SO100 engine only) and a non-default table height offset (the committed model blob is compiled for
-the reference's default).  The observation delays ARE parameters (`joints_observation_delay_secs`, `image_observation_delay_secs`,
+Cameras: `render_depth` casts the scene's six cameras (cameras.ALOHA_CAMERAS) or any cameras.Camera against the collision geometry
+on the GPU (so101_tree_render) - depth and geom ids, from the current or the delayed state; not RGB, and not wired into the observation.
+Not built: a non-default table height offset (the committed model blob is compiled for the reference's default).  The observation delays ARE parameters (`joints_observation_delay_secs`, `image_observation_delay_secs`,
 aloha2_task.py:153-159: whole control steps, handed to the kernels by so101_tree_configure_env), and `physics_state` /
 `delayed_physics_state` come from a device-side delay line (so101_tree_bind_physics_state).  Both reward modes are built: the overlap boxes (default) and the contact sequence
 (`reward_based_on_overlap=False`, hand_over.py:286-338, with `reward_requires_handover`).
@@ -396,6 +397,55 @@ class AlohaEnvironment:
         self.torch.cuda.current_stream(self.device).synchronize()
         s.set_settled_store(first_episode, n_episodes, *(t.data_ptr() for t in self._store))
         return self._store
+
+    # ------------------------------------------------------------------ depth / segmentation cameras (cameras.py)
+    def _ensure_hull_planes(self):
+        """Facet planes of the mesh geoms' hulls, computed from the blob's vertices and handed to the library on first use"""
+        if getattr(self, "_planes_set", False):
+            return
+        from .model import meshes
+        m = blobfmt.unpack(self.task.load_blob("f32")[0])
+        verts = np.asarray(m["mesh_vert"], dtype=np.float64).reshape(-1, 3)
+        adr, chunks = [0], []
+        for t, a, n in zip(m["geom_type"], m["geom_vertadr"], m["geom_vertnum"]):
+            if int(t) == 5:
+                chunks.append(meshes.hull_planes(verts[a:a + n]))
+            adr.append(adr[-1] + (len(chunks[-1]) if int(t) == 5 else 0))
+        planes = np.concatenate(chunks) if chunks else np.zeros((0, 4))
+        with self.torch.cuda.device(self.device):
+            self.sim.set_hull_planes(planes.astype(np.float32), np.asarray(adr, dtype=np.int32))
+        self._planes_set = True
+
+    def render_depth(self, camera, height: int, width: int, env_ids=None, segmentation: bool = True, delayed: bool = False):
+        """Depth and geom-id images of the collision geometry, by ray casting on the GPU (so101_tree_render).
+
+        camera: a name of cameras.ALOHA_CAMERAS, a cameras.Camera (its `body` a body id or a name of `meta["body_names"]`), or a
+        sequence of either (at most 8).
+        env_ids: env indices to render (sequence or tensor), None = all.
+        delayed: False renders the current state, True the state of `image_observation_delay_secs` ago - the qpos of
+        `delayed_physics_state`, what the reference's delayed camera observables show; it needs the env's physics-state line
+        (`physics_state=True` for batches).
+        Returns (depth [n, ncam, height, width] float32, seg int32 of the same shape or None) on the env's device, for any n_envs.
+        depth is the distance along the optical axis, +inf where the ray hits nothing; seg the geom index
+        (`meta["geom_names"][i]` names it), -1 where it hits nothing.  This is not RGB: textures and visual-only meshes are not
+        rendered, and a camera's horizontal extent follows from square pixels."""
+        from . import cameras as _cameras
+        torch = self.torch
+        cams = [c.with_body_ids(self.meta["body_names"]) for c in _cameras.resolve(camera, _cameras.ALOHA_CAMERAS)]
+        if delayed and not self._with_state:
+            raise ValueError("render_depth(delayed=True) needs the physics-state delay line: create the environment with physics_state=True")
+        self._ensure_hull_planes()
+        idx, n = None, self.n_envs
+        if env_ids is not None:
+            idx = torch.as_tensor(env_ids, dtype=torch.int32, device=self.device).reshape(-1).contiguous()
+            n = int(idx.numel())
+            if n == 0 or int(idx.min()) < 0 or int(idx.max()) >= self.n_envs:
+                raise ValueError("env_ids must name at least one env of this batch")
+        depth = torch.empty(n, len(cams), int(height), int(width), dtype=torch.float32, device=self.device)
+        seg = torch.empty(n, len(cams), int(height), int(width), dtype=torch.int32, device=self.device) if segmentation else None
+        self.sim.render([c.spec() for c in cams], height, width, idx.data_ptr() if idx is not None else None, n,
+                        depth.data_ptr(), seg.data_ptr() if seg is not None else None, self._stream(), source=1 if delayed else 0)
+        return depth, seg
 
     def episode_returns(self):
         return self.ep_return

@@ -78,14 +78,7 @@ struct so101_sim : HostHandle {      // (so101_host.hpp: device, owned allocatio
   int last_path = -1, last_chains = 0;                  // so101_get_info
   bool last_graph = false;
   size_t scratch_bytes = 0;
-  // cameras (so101_set_hull_planes / so101_render): host copies of what the plane check reads, the uploaded planes, the frames scratch
-  std::vector<int> h_gtype, h_vertadr, h_vertnum;
-  std::vector<float> h_vert;               // [nvert][3]
-  float* hull_planes = nullptr;            // [n][4] unit outward normal, offset: n . x + d <= 0 inside (geom frame)
-  int* plane_adr = nullptr;                // [ngeom + 1]
-  bool planes_set = false;
-  float *render_frames = nullptr, *render_cams = nullptr;     // [cap][ngeom][RENDER_FRAME], [cap][RENDER_MAXCAM][RENDER_CAMFRAME]
-  size_t render_cap = 0;
+  RenderHost render;                       // cameras (so101_set_hull_planes / so101_render; so101_host.hpp)
 };
 
 namespace {
@@ -236,7 +229,7 @@ int build_model(so101_sim* s, const BlobView& b) {
   }
   // everything else of the geometry is the same in both engines (so101_host.hpp); this one's k_narrow reads the support-vertex lists
   if (!upload_geometry(s, b, gdyn, gp, gm, true, M) || !upload_one(s, M, &s->dm)) return SO101_ERR_HIP;
-  s->h_gtype = b.I("geom_type"); s->h_vertadr = b.I("geom_vertadr"); s->h_vertnum = b.I("geom_vertnum"); s->h_vert = b.F("mesh_vert");
+  s->render.load(b);
   return SO101_OK;
 }
 
@@ -790,25 +783,7 @@ int so101_set_hull_planes(so101_sim* s, const float* planes, const int32_t* plan
   if (!s) return SO101_ERR_ARG;
   if (!planes || !plane_adr) { s->err = "so101_set_hull_planes: NULL argument"; return SO101_ERR_ARG; }
   const int ng = s->hm.ngeom;
-  auto fail = [&](int g, const std::string& what) { s->err = "so101_set_hull_planes: geom " + std::to_string(g) + ": " + what; return (int)SO101_ERR_ARG; };
-  if (plane_adr[0] != 0) return fail(0, "plane_adr must start at 0");
-  for (int g = 0; g < ng; g++) {
-    const int k0 = plane_adr[g], k1 = plane_adr[g + 1];
-    if (k1 < k0 || k1 > (1 << 24)) return fail(g, "plane range is not ascending");
-    if (s->h_gtype[g] != G_MESH) { if (k1 != k0) return fail(g, "not a mesh geom, its plane range must be empty"); continue; }
-    if (k1 - k0 < 4) return fail(g, "a mesh geom needs at least 4 planes");
-    const float* v = &s->h_vert[3 * (size_t)s->h_vertadr[g]];
-    const int nv = s->h_vertnum[g];
-    for (int k = k0; k < k1; k++) {
-      const double nx = planes[4 * (size_t)k], ny = planes[4 * (size_t)k + 1], nz = planes[4 * (size_t)k + 2], d = planes[4 * (size_t)k + 3];
-      const double len = std::sqrt(nx * nx + ny * ny + nz * nz);
-      if (!(std::fabs(len - 1.0) <= 1e-4)) return fail(g, "plane " + std::to_string(k - k0) + " has no unit normal");
-      double top = -1e30;
-      for (int i = 0; i < nv; i++) top = std::max(top, nx * v[3 * i] + ny * v[3 * i + 1] + nz * v[3 * i + 2] + d);
-      if (!(top <= 1e-5)) return fail(g, "plane " + std::to_string(k - k0) + " cuts off a hull vertex");
-      if (!(top >= -1e-5)) return fail(g, "plane " + std::to_string(k - k0) + " touches no hull vertex");
-    }
-  }
+  if (!check_hull_planes(s, "so101_set_hull_planes", s->render, planes, plane_adr)) return SO101_ERR_ARG;          // (so101_host.hpp)
   GUARD_DEVICE(s);
   // (a render in flight reads the old tables: they stay allocated until so101_destroy)
   const size_t n = (size_t)plane_adr[ng];
@@ -816,46 +791,32 @@ int so101_set_hull_planes(so101_sim* s, const float* planes, const int32_t* plan
   if (!scratch_alloc(s, &dp, 4 * n, -1, "hipMalloc(hull planes)") || !scratch_alloc(s, &da, (size_t)ng + 1, -1, "hipMalloc(hull planes)")) return SO101_ERR_HIP;
   if (n && !hip_ok(s, hipMemcpy(dp, planes, sizeof(float) * 4 * n, hipMemcpyHostToDevice), "hipMemcpy(hull planes)")) return SO101_ERR_HIP;
   if (!hip_ok(s, hipMemcpy(da, plane_adr, sizeof(int) * ((size_t)ng + 1), hipMemcpyHostToDevice), "hipMemcpy(hull planes)")) return SO101_ERR_HIP;
-  s->hull_planes = dp; s->plane_adr = da; s->planes_set = true;
+  s->render.hull_planes = dp; s->render.plane_adr = da; s->render.planes_set = true;
   return SO101_OK;
 }
 
 int so101_render(so101_sim* s, const so101_camera* cams, int ncam, int height, int width, const int32_t* env_index, int n_render,
                  float* depth, int32_t* seg, void* stream) {
   REQUIRE_BOUND(s);
-  if (!cams || ncam < 1 || ncam > RENDER_MAXCAM || height < 1 || height > 4096 || width < 1 || width > 4096 || n_render < 1 || (!depth && !seg)) {
-    s->err = "so101_render: bad argument (1 <= ncam <= 8, 1 <= height, width <= 4096, n_render >= 1, depth or seg)"; return SO101_ERR_ARG;
-  }
-  if (!env_index && n_render > s->n_envs) { s->err = "so101_render: n_render exceeds the envs of the handle"; return SO101_ERR_ARG; }
-  const unsigned long long blocks = (unsigned long long)n_render * ncam * ((height + 7) / 8) * ((width + 7) / 8);
-  if (blocks > 0x7fffffffull) { s->err = "so101_render: more than 2^31 - 1 pixel tiles in one call"; return SO101_ERR_ARG; }
   RenderCams rc{};
-  for (int k = 0; k < ncam; k++) {
-    if (cams[k].body < -1 || cams[k].body >= NDYN || !(cams[k].fovy_deg > 0.f && cams[k].fovy_deg < 180.f)) {
-      s->err = "so101_render: camera " + std::to_string(k) + ": body must be -1 .. 7 and 0 < fovy_deg < 180"; return SO101_ERR_ARG;
-    }
-    rc.cam[k].body = cams[k].body;
-    rc.cam[k].scale = (float)(2.0 * std::tan(0.5 * (double)cams[k].fovy_deg * 3.14159265358979323846 / 180.0) / (double)height);
-    memcpy(rc.cam[k].pos, cams[k].pos, sizeof rc.cam[k].pos); memcpy(rc.cam[k].mat, cams[k].mat, sizeof rc.cam[k].mat);
-  }
-  bool meshes = false;
-  for (int t : s->h_gtype) meshes = meshes || t == G_MESH;
-  if (meshes && !s->planes_set) { s->err = "so101_render: the scene has mesh geoms and no hull planes (call so101_set_hull_planes)"; return SO101_ERR_STATE; }
+  if (!render_arguments(s, "so101_render", cams, ncam, height, width, n_render, s->n_envs, env_index != nullptr, depth || seg, NDYN - 1, rc)) return SO101_ERR_ARG;
+  RenderHost& R = s->render;
+  if (R.has_meshes() && !R.planes_set) { s->err = "so101_render: the scene has mesh geoms and no hull planes (call so101_set_hull_planes)"; return SO101_ERR_STATE; }
   GUARD_DEVICE(s);
-  if ((size_t)n_render > s->render_cap) {
+  if ((size_t)n_render > R.cap) {
     // grown outside any stream order: hipFree waits for the device, so a render still reading the old scratch finishes first
-    for (void* p : {(void*)s->render_frames, (void*)s->render_cams}) {
+    for (void* p : {(void*)R.frames, (void*)R.cams}) {
       auto it = std::find(s->owned.begin(), s->owned.end(), p);
       if (p && it != s->owned.end()) { s->owned.erase(it); (void)hipFree(p); }
     }
-    s->scratch_bytes -= sizeof(float) * s->render_cap * ((size_t)s->hm.ngeom * RENDER_FRAME + RENDER_MAXCAM * RENDER_CAMFRAME);
-    s->render_frames = nullptr; s->render_cams = nullptr; s->render_cap = 0;
-    if (!scratch_alloc(s, &s->render_frames, (size_t)n_render * s->hm.ngeom * RENDER_FRAME, -1, "hipMalloc(render)") ||
-        !scratch_alloc(s, &s->render_cams, (size_t)n_render * RENDER_MAXCAM * RENDER_CAMFRAME, -1, "hipMalloc(render)")) return SO101_ERR_HIP;
-    s->render_cap = (size_t)n_render;
+    s->scratch_bytes -= sizeof(float) * R.cap * ((size_t)s->hm.ngeom * RENDER_FRAME + RENDER_MAXCAM * RENDER_CAMFRAME);
+    R.frames = nullptr; R.cams = nullptr; R.cap = 0;
+    if (!scratch_alloc(s, &R.frames, (size_t)n_render * s->hm.ngeom * RENDER_FRAME, -1, "hipMalloc(render)") ||
+        !scratch_alloc(s, &R.cams, (size_t)n_render * RENDER_MAXCAM * RENDER_CAMFRAME, -1, "hipMalloc(render)")) return SO101_ERR_HIP;
+    R.cap = (size_t)n_render;
   }
   so101::launch_render(n_render, (hipStream_t)stream, s->dm, make_params(s), s->buf, (const int*)env_index, rc, ncam, height, width,
-                       s->hull_planes, s->plane_adr, s->render_frames, s->render_cams, depth, (int*)seg);
+                       R.hull_planes, R.plane_adr, R.frames, R.cams, depth, (int*)seg);
   LAUNCH_CHECK(s, "k_render");
   return SO101_OK;
 }

@@ -9,7 +9,9 @@
 #include "so101_tables.hpp"
 
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -149,4 +151,68 @@ inline bool upload_geometry(HostHandle* s, const BlobView& b, const std::vector<
          upload(s, b.F("geom_solimp"), &M.geom_solimp) && upload(s, b.F("geom_center"), &M.geom_center) && upload(s, b.F("geom_aabb"), &M.geom_aabb) &&
          upload(s, b.F("geom_rbound"), &M.geom_rbound) && upload(s, vx, &M.vx) && upload(s, vy, &M.vy) && upload(s, vz, &M.vz) &&
          upload(s, pairs, &M.pair) && upload(s, packed, &M.pair_packed);
+}
+
+// ---------------------------------------------------------------------------------------------------- depth / segmentation cameras
+// What both handles keep for so101_set_hull_planes / so101_render and their so101_tree_* twins: host copies of what the plane check reads, the
+// uploaded planes, the frames scratch of the render calls.
+struct RenderHost {
+  std::vector<int> gtype, vertadr, vertnum;
+  std::vector<float> vert;                 // [nvert][3]
+  float* hull_planes = nullptr;            // device [n][4] unit outward normal, offset: n . x + d <= 0 inside (geom frame)
+  int* plane_adr = nullptr;                // device [ngeom + 1]
+  bool planes_set = false;
+  float *frames = nullptr, *cams = nullptr;      // device [cap][ngeom][RENDER_FRAME], [cap][RENDER_MAXCAM][RENDER_CAMFRAME]
+  size_t cap = 0;
+  void load(const BlobView& b) { gtype = b.I("geom_type"); vertadr = b.I("geom_vertadr"); vertnum = b.I("geom_vertnum"); vert = b.F("mesh_vert"); }
+  bool has_meshes() const { for (int t : gtype) if (t == G_MESH) return true; return false; }
+};
+
+// The contract of so101_set_hull_planes (include/so101.h) on HOST arrays, before anything is uploaded: non-mesh geoms have empty ranges, a mesh
+// geom has at least 4 planes, | |n| - 1 | <= 1e-4, every vertex of the hull has n . v + d <= 1e-5, every plane has a vertex within 1e-5 of it.
+// false with "<api>: geom <g>: <what>" in s->err.
+inline bool check_hull_planes(HostHandle* s, const char* api, const RenderHost& R, const float* planes, const int32_t* plane_adr) {
+  const int ng = (int)R.gtype.size();
+  auto fail = [&](int g, const std::string& what) { s->err = std::string(api) + ": geom " + std::to_string(g) + ": " + what; return false; };
+  if (plane_adr[0] != 0) return fail(0, "plane_adr must start at 0");
+  for (int g = 0; g < ng; g++) {
+    const int k0 = plane_adr[g], k1 = plane_adr[g + 1];
+    if (k1 < k0 || k1 > (1 << 24)) return fail(g, "plane range is not ascending");
+    if (R.gtype[g] != G_MESH) { if (k1 != k0) return fail(g, "not a mesh geom, its plane range must be empty"); continue; }
+    if (k1 - k0 < 4) return fail(g, "a mesh geom needs at least 4 planes");
+    const float* v = &R.vert[3 * (size_t)R.vertadr[g]];
+    const int nv = R.vertnum[g];
+    for (int k = k0; k < k1; k++) {
+      const double nx = planes[4 * (size_t)k], ny = planes[4 * (size_t)k + 1], nz = planes[4 * (size_t)k + 2], d = planes[4 * (size_t)k + 3];
+      const double len = std::sqrt(nx * nx + ny * ny + nz * nz);
+      if (!(std::fabs(len - 1.0) <= 1e-4)) return fail(g, "plane " + std::to_string(k - k0) + " has no unit normal");
+      double top = -1e30;
+      for (int i = 0; i < nv; i++) top = std::max(top, nx * v[3 * i] + ny * v[3 * i + 1] + nz * v[3 * i + 2] + d);
+      if (!(top <= 1e-5)) return fail(g, "plane " + std::to_string(k - k0) + " cuts off a hull vertex");
+      if (!(top >= -1e-5)) return fail(g, "plane " + std::to_string(k - k0) + " touches no hull vertex");
+    }
+  }
+  return true;
+}
+
+// The arguments of a render call that no engine reads differently: counts, sizes, the tile count, and the cameras into the kernel argument
+// (pixel scale 2 tan(fovy / 2) / H in double).  body_max: the highest body a camera may be fixed to.  false (SO101_ERR_ARG) with s->err set.
+inline bool render_arguments(HostHandle* s, const char* api, const so101_camera* cams, int ncam, int height, int width, int n_render, int n_envs,
+                             bool has_index, bool has_output, int body_max, RenderCams& rc) {
+  const std::string a(api);
+  if (!cams || ncam < 1 || ncam > RENDER_MAXCAM || height < 1 || height > 4096 || width < 1 || width > 4096 || n_render < 1 || !has_output) {
+    s->err = a + ": bad argument (1 <= ncam <= 8, 1 <= height, width <= 4096, n_render >= 1, depth or seg)"; return false;
+  }
+  if (!has_index && n_render > n_envs) { s->err = a + ": n_render exceeds the envs of the handle"; return false; }
+  const unsigned long long blocks = (unsigned long long)n_render * ncam * ((height + 7) / 8) * ((width + 7) / 8);
+  if (blocks > 0x7fffffffull) { s->err = a + ": more than 2^31 - 1 pixel tiles in one call"; return false; }
+  for (int k = 0; k < ncam; k++) {
+    if (cams[k].body < -1 || cams[k].body > body_max || !(cams[k].fovy_deg > 0.f && cams[k].fovy_deg < 180.f)) {
+      s->err = a + ": camera " + std::to_string(k) + ": body must be -1 .. " + std::to_string(body_max) + " and 0 < fovy_deg < 180"; return false;
+    }
+    rc.cam[k].body = cams[k].body;
+    rc.cam[k].scale = (float)(2.0 * std::tan(0.5 * (double)cams[k].fovy_deg * 3.14159265358979323846 / 180.0) / (double)height);
+    memcpy(rc.cam[k].pos, cams[k].pos, sizeof rc.cam[k].pos); memcpy(rc.cam[k].mat, cams[k].mat, sizeof rc.cam[k].mat);
+  }
+  return true;
 }

@@ -26,7 +26,11 @@ void launch_debug_forward(int solver, int n_envs, hipStream_t st, const DevModel
 void launch_begin(int n_envs, hipStream_t st, const DevModel* m, const StepParams& P, const DevBuffers& B, unsigned char* need_reset);
 void launch_reward(int n_envs, hipStream_t st, const DevModel* m, const StepParams& P, const DevBuffers& B, float* reward);
 
-// depth / segmentation cameras (so101_camera.hpp): frames of n_render envs, then one wavefront per 8 x 8 tile of every (env, camera) image
+// depth / segmentation cameras.  launch_render_image: k_render (so101_raycast.hpp), one wavefront per 8 x 8 tile of every (env, camera) image, from
+// frames an engine's frames kernel published on the same stream - the ONE copy of k_render in the library, called by both engines (the
+// general-tree engine after its k_tree_render_frames, tu_tree.hip).  launch_render: the SO100 frames kernel (so101_camera.hpp), then the image.
+void launch_render_image(int n_render, hipStream_t st, const DevModel* m, const float* frames, const float* camframes, const float* planes, const int* plane_adr,
+                         int ncam, int height, int width, float* depth, int* seg);
 void launch_render(int n_render, hipStream_t st, const DevModel* m, const StepParams& P, const DevBuffers& B, const int* env_index, const RenderCams& cams,
                    int ncam, int height, int width, const float* planes, const int* plane_adr, float* frames, float* camframes,
                    float* depth, int* seg);

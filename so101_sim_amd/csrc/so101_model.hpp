@@ -283,9 +283,10 @@ struct ChainParams { const DevModel* m; StepParams P; DevBuffers B; EventBuffers
 #define DBG_REWARD (DBG_ROWF + 16)
 #define DBG_DIM 2048
 
-// ---- depth / segmentation cameras (so101_camera.hpp): scratch layouts and the cameras of one so101_render call (a kernel argument)
+// ---- depth / segmentation cameras (so101_raycast.hpp, so101_camera.hpp, tu_tree.hip): scratch layouts and the cameras of one so101_render /
+// so101_tree_render call (a kernel argument)
 #define RENDER_MAXCAM 8
 #define RENDER_FRAME 16          // floats per geom: R[9] (world from geom), p[3], bounding-sphere centre[3], radius (< 0: never hit)
 #define RENDER_CAMFRAME 13       // floats per camera: pos[3], mat[9] (world from camera; columns x right, y up, z; the camera looks along -z), pixel scale
-struct RenderCam { int body; float pos[3], mat[9], scale; };      // body: -1 world, 0 .. NDYN - 1 as geom_dyn numbers the dynamic bodies; scale = 2 tan(fovy / 2) / H
+struct RenderCam { int body; float pos[3], mat[9], scale; };      // body: -1 world, else as geom_dyn numbers the bodies (SO100: 0 .. NDYN - 1, tree: the body id); scale = 2 tan(fovy / 2) / H
 struct RenderCams { RenderCam cam[RENDER_MAXCAM]; };

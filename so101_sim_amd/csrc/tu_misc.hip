@@ -43,12 +43,16 @@ void launch_begin(int n_envs, hipStream_t st, const DevModel* m, const StepParam
 void launch_reward(int n_envs, hipStream_t st, const DevModel* m, const StepParams& P, const DevBuffers& B, float* reward) {
   hipLaunchKernelGGL(k_reward, dim3(n_envs), dim3(64), 0, st, m, P, B, reward);
 }
+void launch_render_image(int n_render, hipStream_t st, const DevModel* m, const float* frames, const float* camframes, const float* planes, const int* plane_adr,
+                         int ncam, int height, int width, float* depth, int* seg) {
+  unsigned int tiles = (unsigned int)((height + 7) / 8) * (unsigned int)((width + 7) / 8);
+  hipLaunchKernelGGL(k_render, dim3((unsigned int)n_render * (unsigned int)ncam * tiles), dim3(64), 0, st, m, frames, camframes, planes, plane_adr, ncam, height, width,
+                     depth, seg);
+}
 void launch_render(int n_render, hipStream_t st, const DevModel* m, const StepParams& P, const DevBuffers& B, const int* env_index, const RenderCams& cams,
                    int ncam, int height, int width, const float* planes, const int* plane_adr, float* frames, float* camframes,
                    float* depth, int* seg) {
   hipLaunchKernelGGL(k_render_frames, dim3(n_render), dim3(64), 0, st, m, P, B, env_index, cams, ncam, frames, camframes);
-  unsigned int tiles = (unsigned int)((height + 7) / 8) * (unsigned int)((width + 7) / 8);
-  hipLaunchKernelGGL(k_render, dim3((unsigned int)n_render * (unsigned int)ncam * tiles), dim3(64), 0, st, m, frames, camframes, planes, plane_adr, ncam, height, width,
-                     depth, seg);
+  launch_render_image(n_render, st, m, frames, camframes, planes, plane_adr, ncam, height, width, depth, seg);
 }
 }  // namespace so101

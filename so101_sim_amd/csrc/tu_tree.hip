@@ -2,6 +2,7 @@
 // Kernels and their launches live in one translation unit (no relocatable device code).
 #include <hip/hip_runtime.h>
 #include "so101_host.hpp"
+#include "so101_launch.hpp"
 #include "so101_tree.hpp"
 
 #include <algorithm>
@@ -434,6 +435,56 @@ __global__ void __launch_bounds__(64, 2) k_tree_pipe_finish(const TreeModel* tm,
   tree_finish_step<2>(tm, gm, T, L, G, B, E, e, act == 2, obs, reward, discount, step_type, &P);
 }
 
+// ---- depth / segmentation cameras (so101_tree_render of include/so101.h): the frames kernel of this engine, one wavefront per rendered env.
+// It runs the engine's own kinematics on the qpos of the selected source - q[lane * lane_stride + e * env_stride]: the bound state
+// (qpos[nq][N], env-fastest) or the delayed physics-state line ([N][nq + nv], its first nq entries) - and publishes what k_render
+// (so101_raycast.hpp) consumes, record for record as k_render_frames (so101_camera.hpp) does for SO100: per geom the world frame of
+// load_geom_at(), the bounding-sphere centre and geom_rbound (-1: the env index is outside [0, N), nothing of that image can be hit), per
+// camera its world frame.  A camera is fixed to the world (body -1 or 0: kinematics() keeps the identity there) or to a tree body.
+__global__ void __launch_bounds__(64) k_tree_render_frames(const TreeModel* tm, const DevModel* gm, const float* q, size_t lane_stride, size_t env_stride, int N,
+                                                           const int* env_index, RenderCams cams, int ncam, float* frames, float* camframes) {
+  BLOCK_SHARED(TreeLDS, L);
+  const int i = blockIdx.x, lane = wave_lane();
+  int e = env_index ? env_index[i] : i;
+  e = wave_uniform_i(e);
+  const bool ok = e >= 0 && e < N;
+  if (lane < tm->nq) L.qpos[lane] = q[(size_t)lane * lane_stride + (size_t)(ok ? e : 0) * env_stride];
+  wave_sync();
+  tree::kinematics(tm, L);
+  const int ngeom = gm->ngeom;
+  for (int g = lane; g < ngeom; g += WAVE) {
+    int b = gm->geom_dyn[g];            // (this engine's geom_dyn is the body id)
+    GeomW G;
+    load_geom_at<G16>(gm, g, L.xpos[b], L.xmat[b], G);
+    float* f = frames + ((size_t)i * ngeom + g) * RENDER_FRAME;
+#pragma unroll
+    for (int k = 0; k < 9; k++) f[k] = G.R[k];
+#pragma unroll
+    for (int k = 0; k < 3; k++) { f[9 + k] = G.p[k]; f[12 + k] = G.c[k]; }
+    f[15] = ok ? gm->geom_rbound[g] : -1.f;
+  }
+  // cameras: composed with their body's pose on wave-uniform values (constant indices into the kernel argument), lane 0 publishes
+#pragma unroll
+  for (int k = 0; k < RENDER_MAXCAM; k++) {
+    if (k >= ncam) break;
+    const int b = cams.cam[k].body < 0 ? 0 : cams.cam[k].body;
+    float X[9], P0[3], cp[3], cm[9];
+#pragma unroll
+    for (int j = 0; j < 9; j++) { X[j] = L.xmat[b][j]; cm[j] = cams.cam[k].mat[j]; }
+#pragma unroll
+    for (int j = 0; j < 3; j++) { P0[j] = L.xpos[b][j]; cp[j] = cams.cam[k].pos[j]; }
+    float t[3], M[9]; matvec3(t, X, cp); matmul3(M, X, cm);
+    if (lane == 0) {
+      float* f = camframes + ((size_t)i * ncam + k) * RENDER_CAMFRAME;
+#pragma unroll
+      for (int j = 0; j < 3; j++) f[j] = P0[j] + t[j];
+#pragma unroll
+      for (int j = 0; j < 9; j++) f[3 + j] = M[j];
+      f[12] = cams.cam[k].scale;
+    }
+  }
+}
+
 // ==================================================================================================== host side
 struct TreeHandle : HostHandle {      // (so101_host.hpp: device, owned allocations, err)
   int n_envs = 0;
@@ -459,6 +510,7 @@ struct TreeHandle : HostHandle {      // (so101_host.hpp: device, owned allocati
   static constexpr int MAXSLICES = 4;
   hipStream_t slice_stream[MAXSLICES] = {};      // env slices whose chains overlap (one's narrowphase beside another's solve)
   hipEvent_t slice_begin = nullptr, slice_done[MAXSLICES] = {};
+  RenderHost render;                   // cameras (so101_tree_set_hull_planes / so101_tree_render; so101_host.hpp)
   int plan[4] = {0, 0, 0, 0};          // what the last so101_tree_step enqueued: env slices, kernel launches, memsets, path (0 none yet, 1 single kernel, 2 launch chain)
 };
 
@@ -613,6 +665,7 @@ int tree_build(TreeHandle* s, const BlobView& b) {
     for (int k = 0; k < M.nu; k++) T.home_ctrl[k] = hc[k];
   }
   if (!upload_one(s, M, &s->dm) || !upload_one(s, G, &s->dg)) return SO101_ERR_HIP;
+  s->render.load(b);
   return SO101_OK;
 }
 }  // namespace
@@ -910,6 +963,54 @@ int TAPI(begin_episode)(TreeHandle* s, void* stream) {
   GUARD_DEVICE(s);
   hipLaunchKernelGGL(k_tree_begin, dim3(s->n_envs), dim3(64), 0, (hipStream_t)stream, s->dm, task_now(s), s->buf, s->env);
   return hip_ok(s, hipGetLastError(), "k_tree_begin") ? SO101_OK : SO101_ERR_HIP;
+}
+
+// ---- cameras (k_tree_render_frames above, then the library's one k_render through so101::launch_render_image)
+int TAPI(set_hull_planes)(TreeHandle* s, const float* planes, const int32_t* plane_adr) {
+  if (!s) return SO101_ERR_ARG;
+  if (!planes || !plane_adr) { s->err = "so101_tree_set_hull_planes: NULL argument"; return SO101_ERR_ARG; }
+  if (!check_hull_planes(s, "so101_tree_set_hull_planes", s->render, planes, plane_adr)) return SO101_ERR_ARG;          // (so101_host.hpp)
+  GUARD_DEVICE(s);
+  // (a render in flight reads the old tables: they stay allocated until so101_tree_destroy)
+  const int ng = s->hm.ngeom;
+  const size_t n = (size_t)plane_adr[ng];
+  float* dp = nullptr; int* da = nullptr;
+  if (!dev_alloc(s, &dp, 4 * n, -1, "hipMalloc(hull planes)") || !dev_alloc(s, &da, (size_t)ng + 1, -1, "hipMalloc(hull planes)")) return SO101_ERR_HIP;
+  if (n && !hip_ok(s, hipMemcpy(dp, planes, sizeof(float) * 4 * n, hipMemcpyHostToDevice), "hipMemcpy(hull planes)")) return SO101_ERR_HIP;
+  if (!hip_ok(s, hipMemcpy(da, plane_adr, sizeof(int) * ((size_t)ng + 1), hipMemcpyHostToDevice), "hipMemcpy(hull planes)")) return SO101_ERR_HIP;
+  s->render.hull_planes = dp; s->render.plane_adr = da; s->render.planes_set = true;
+  return SO101_OK;
+}
+
+int TAPI(render)(TreeHandle* s, const so101_camera* cams, int ncam, int height, int width, const int32_t* env_index, int n_render, int source,
+                 float* depth, int32_t* seg, void* stream) {
+  if (!s) return SO101_ERR_ARG;
+  RenderCams rc{};
+  if (!render_arguments(s, "so101_tree_render", cams, ncam, height, width, n_render, s->n_envs, env_index != nullptr, depth || seg, s->hm.nbody - 1, rc)) return SO101_ERR_ARG;
+  if (source != 0 && source != 1) { s->err = "so101_tree_render: source must be 0 (the bound qpos) or 1 (the delayed physics-state line)"; return SO101_ERR_ARG; }
+  RenderHost& R = s->render;
+  if (R.has_meshes() && !R.planes_set) { s->err = "so101_tree_render: the scene has mesh geoms and no hull planes (call so101_tree_set_hull_planes)"; return SO101_ERR_STATE; }
+  if (source == 0 && !s->bound) { s->err = "so101_tree_render before so101_tree_bind_state"; return SO101_ERR_STATE; }
+  if (source == 1 && !s->env.ps_delayed) { s->err = "so101_tree_render: source 1 needs the physics-state line (so101_tree_bind_physics_state)"; return SO101_ERR_STATE; }
+  GUARD_DEVICE(s);
+  const size_t ng = (size_t)s->hm.ngeom;
+  if ((size_t)n_render > R.cap) {
+    // grown outside any stream order: hipFree waits for the device, so a render still reading the old scratch finishes first
+    for (void* p : {(void*)R.frames, (void*)R.cams}) {
+      auto it = std::find(s->owned.begin(), s->owned.end(), p);
+      if (p && it != s->owned.end()) { s->owned.erase(it); (void)hipFree(p); }
+    }
+    R.frames = nullptr; R.cams = nullptr; R.cap = 0;
+    if (!dev_alloc(s, &R.frames, (size_t)n_render * ng * RENDER_FRAME, -1, "hipMalloc(render)") ||
+        !dev_alloc(s, &R.cams, (size_t)n_render * RENDER_MAXCAM * RENDER_CAMFRAME, -1, "hipMalloc(render)")) return SO101_ERR_HIP;
+    R.cap = (size_t)n_render;
+  }
+  const float* q = source == 0 ? s->buf.qpos : s->env.ps_delayed;
+  const size_t lane_stride = source == 0 ? (size_t)s->n_envs : 1, env_stride = source == 0 ? 1 : (size_t)(s->hm.nq + s->hm.nv);
+  hipLaunchKernelGGL(k_tree_render_frames, dim3(n_render), dim3(64), 0, (hipStream_t)stream, s->dm, s->dg, q, lane_stride, env_stride, s->n_envs, (const int*)env_index, rc, ncam,
+                     R.frames, R.cams);
+  so101::launch_render_image(n_render, (hipStream_t)stream, s->dg, R.frames, R.cams, R.hull_planes, R.plane_adr, ncam, height, width, depth, (int*)seg);
+  return hip_ok(s, hipGetLastError(), "k_render") ? SO101_OK : SO101_ERR_HIP;
 }
 
 int TAPI(get_diag)(TreeHandle* s, int* out /* [n_envs][8] device or host-visible memory */, void* stream) {

@@ -27,7 +27,9 @@
   int so101_tree##V##_set_settled_store(void*, int, int, const float*, const float*, const float*, const int32_t*);                           \
   int so101_tree##V##_settle(void*, void*);                                                                                                   \
   int so101_tree##V##_begin_episode(void*, void*);                                                                                            \
-  int so101_tree##V##_step(void*, const float*, float*, float*, float*, uint8_t*, void*);
+  int so101_tree##V##_step(void*, const float*, float*, float*, float*, uint8_t*, void*);                                                     \
+  int so101_tree##V##_set_hull_planes(void*, const float*, const int32_t*);                                                                   \
+  int so101_tree##V##_render(void*, const so101_camera*, int, int, int, const int32_t*, int, int, float*, int32_t*, void*);
 
 // (the builds define these with their own handle type in place of void*: same C symbol, same calling convention)
 extern "C" {
@@ -97,6 +99,11 @@ int so101_tree_settle(so101_tree* s, void* stream) { return s ? FWD(settle, stre
 int so101_tree_begin_episode(so101_tree* s, void* stream) { return s ? FWD(begin_episode, stream) : SO101_ERR_ARG; }
 int so101_tree_step(so101_tree* s, const float* action, float* obs, float* reward, float* discount, uint8_t* step_type, void* stream) {
   return s ? FWD(step, action, obs, reward, discount, step_type, stream) : SO101_ERR_ARG;
+}
+int so101_tree_set_hull_planes(so101_tree* s, const float* planes, const int32_t* plane_adr) { return s ? FWD(set_hull_planes, planes, plane_adr) : SO101_ERR_ARG; }
+int so101_tree_render(so101_tree* s, const so101_camera* cams, int ncam, int height, int width, const int32_t* env_index, int n_render, int source,
+                      float* depth, int32_t* seg, void* stream) {
+  return s ? FWD(render, cams, ncam, height, width, env_index, n_render, source, depth, seg, stream) : SO101_ERR_ARG;
 }
 
 }  // extern "C"

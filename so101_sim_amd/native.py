@@ -35,7 +35,7 @@ EXPORTS = (
     "so101_set_hull_planes", "so101_render",
     "so101_tree_create", "so101_tree_destroy", "so101_tree_dims", "so101_tree_last_plan", "so101_tree_bind_state", "so101_tree_configure", "so101_tree_physics",
     "so101_tree_debug_forward", "so101_tree_get_diag", "so101_tree_last_error", "so101_tree_obs_dim", "so101_tree_bind_env",
-    "so101_tree_configure_env", "so101_tree_bind_physics_state", "so101_tree_reset", "so101_tree_step", "so101_tree_begin_episode", "so101_tree_settle", "so101_tree_compute_settled", "so101_tree_set_settled_store",
+    "so101_tree_configure_env", "so101_tree_bind_physics_state", "so101_tree_reset", "so101_tree_step", "so101_tree_set_hull_planes", "so101_tree_render", "so101_tree_begin_episode", "so101_tree_settle", "so101_tree_compute_settled", "so101_tree_set_settled_store",
 )
 
 
@@ -56,6 +56,17 @@ class Config(C.Structure):
 class CameraSpec(C.Structure):
     """so101_camera of include/so101.h"""
     _fields_ = [("body", C.c_int32), ("pos", C.c_float * 3), ("mat", C.c_float * 9), ("fovy_deg", C.c_float)]
+
+
+def camera_array(cams):
+    """(body, pos[3], mat[9] row-major, fovy_deg) tuples as the so101_camera array of so101_render / so101_tree_render"""
+    arr = (CameraSpec * max(len(cams), 1))()
+    for k, (body, pos, mat, fovy) in enumerate(cams):
+        arr[k].body = int(body)
+        arr[k].pos[:] = [float(x) for x in pos]
+        arr[k].mat[:] = [float(x) for x in mat]
+        arr[k].fovy_deg = float(fovy)
+    return arr
 
 
 _libs: dict[str, C.CDLL] = {}
@@ -235,12 +246,7 @@ class Sim:
 
     def render(self, cams, height: int, width: int, env_index, n_render: int, depth, seg, stream=0):
         """cams: sequence of (body, pos[3], mat[9] row-major, fovy_deg); env_index / depth / seg: raw device addresses or None"""
-        arr = (CameraSpec * max(len(cams), 1))()
-        for k, (body, pos, mat, fovy) in enumerate(cams):
-            arr[k].body = int(body)
-            arr[k].pos[:] = [float(x) for x in pos]
-            arr[k].mat[:] = [float(x) for x in mat]
-            arr[k].fovy_deg = float(fovy)
+        arr = camera_array(cams)
         self._check(self.L.so101_render(self.h, arr, len(cams), int(height), int(width), env_index, int(n_render), depth, seg, stream), "so101_render")
 
 
@@ -282,6 +288,8 @@ class TreeSim:
         L.so101_tree_settle.argtypes = [C.c_void_p, C.c_void_p]
         L.so101_tree_compute_settled.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5
         L.so101_tree_set_settled_store.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4
+        L.so101_tree_set_hull_planes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.so101_tree_render.argtypes = [C.c_void_p, C.POINTER(CameraSpec), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         self.n_envs = int(n_envs)
         h = C.c_void_p()
         rc = L.so101_tree_create(blob_f32, len(blob_f32), self.n_envs, int(device), C.byref(h))
@@ -369,3 +377,16 @@ class TreeSim:
 
     def set_settled_store(self, first_episode, count, qpos, qvel, warm, flags):
         self._check(self.L.so101_tree_set_settled_store(self.h, int(first_episode), int(count), qpos, qvel, warm, flags), "so101_tree_set_settled_store")
+
+    def set_hull_planes(self, planes, plane_adr):
+        """planes [n, 4] float32 and plane_adr [ngeom + 1] int32: HOST numpy arrays (so101_tree_set_hull_planes copies them)"""
+        import numpy as np
+        planes = np.ascontiguousarray(planes, dtype=np.float32).reshape(-1, 4)
+        plane_adr = np.ascontiguousarray(plane_adr, dtype=np.int32)
+        self._check(self.L.so101_tree_set_hull_planes(self.h, planes.ctypes.data, plane_adr.ctypes.data), "so101_tree_set_hull_planes")
+
+    def render(self, cams, height: int, width: int, env_index, n_render: int, depth, seg, stream=0, source: int = 0):
+        """cams: sequence of (body, pos[3], mat[9] row-major, fovy_deg), body a tree body id (-1 or 0: the world); env_index / depth / seg: raw
+        device addresses or None; source 0: the bound qpos, 1: the delayed physics-state line (so101_tree_bind_physics_state)"""
+        arr = camera_array(cams)
+        self._check(self.L.so101_tree_render(self.h, arr, len(cams), int(height), int(width), env_index, int(n_render), int(source), depth, seg, stream), "so101_tree_render")
