@@ -34,7 +34,8 @@ extern "C" {
 #endif
 
 #define SO101_ABI_VERSION 10     /* 10: so101_tree_last_plan, and (additions that change nothing older, so the number stays) the cameras: so101_camera,
-                                    so101_set_hull_planes, so101_render, so101_tree_set_hull_planes, so101_tree_render; 9: so101_tree_config gains the observation delays, so101_tree_bind_physics_state; 8: the general-tree engine (so101_tree_*) */
+                                    so101_set_hull_planes, so101_render, so101_tree_set_hull_planes, so101_tree_render, and Cartesian tool control: so101_tool, so101_ik_config, so101_ik_default_config,
+                                    so101_tool_pose, so101_tool_ik; 9: so101_tree_config gains the observation delays, so101_tree_bind_physics_state; 8: the general-tree engine (so101_tree_*) */
 #define SO101_OBS_DIM 18      /* joints_pos(6, delayed) | undelayed_joints_pos(6) | commanded_joints_pos(6) */
 #define SO101_ACT_DIM 6
 #define SO101_SOLVER_PGS 0
@@ -278,6 +279,60 @@ typedef struct {
  * the camera and (r, c, height, width) only.  SO101_ERR_STATE while the scene has mesh geoms and so101_set_hull_planes has not been called. */
 int so101_render(so101_sim* sim, const so101_camera* cams, int ncam, int height, int width, const int32_t* env_index, int n_render,
                  float* depth, int32_t* seg, void* hip_stream);
+
+/* ---- Cartesian tool control (csrc/so101_tool.hpp): the pose and Jacobian of a frame fixed to an arm link, and the inverse map, for thousands of
+ * envs per call on the device.  so101_tool_pose stands in for physics.named.data.site_xpos / site_xmat and mujoco.mj_jacSite of the reference;
+ * so101_tool_ik for dm_control's qpos_from_site_pose (dm_control/utils/inverse_kinematics.py), which the reference's data generator approximates by
+ * hand (examples/automated_lerobot_dataset_generator.py:180 _inverse_kinematics_approximate).  SO100 engine only so far.  Additions: the ABI number stays. */
+typedef struct {
+  int32_t body;       /* 0..5: arm link in chain order, the numbering of so101_camera.body */
+  float pos[3];       /* the tool frame in that body's frame */
+  float mat[9];       /* row-major, orthonormal (|M^T M - I| <= 1e-4 entrywise) */
+} so101_tool;
+typedef struct {
+  int32_t mode;       /* what the solve drives to zero besides the position error: 0 nothing, 1 the angle between the tool's z axis and the target's,
+                         2 the full orientation error */
+  int32_t max_iters;  /* 0..1000 */
+  float tol_pos;      /* metres, > 0 */
+  float tol_rot;      /* radians, > 0 */
+  float rot_weight;   /* metres per radian: weight of the orientation rows, > 0 */
+  float damping;      /* >= 0, added to the error-proportional damping */
+  float max_step;     /* radians: largest joint change of one iteration, > 0 */
+  float q_lo[6], q_hi[6];   /* joint limits the iterates are clamped to, q_lo <= q_hi */
+} so101_ik_config;
+/* mode 1, 60 iterations, 1e-4 m, 1e-3 rad, weight 0.1, damping 1e-6, 0.5 rad per iteration, the model's jnt_range */
+int so101_ik_default_config(const so101_sim* sim, so101_ik_config* cfg);
+/* Tool pose of n entries: pos[n][3] = xpos_b + R_b tool.pos, mat[n][9] = R_b tool.mat (row-major) and jac[n][6][6] (row-major, MuJoCo's mj_jacSite:
+ * rows 0-2 jacp, rows 3-5 jacr; column j = (a_j x (p - o_j), a_j) with a_j the world axis of joint j and o_j the world origin of arm link j; columns of
+ * joints beyond the tool's link are zero).  Any output may be NULL, but not all.  q: DEVICE [n][6] joint angles, row-major like `action`, or NULL = the
+ * arm joints of the bound qpos; env_index (only with q == NULL): DEVICE array of n env indices, NULL = envs 0 .. n - 1 (then n <= n_envs).  An
+ * env_index entry outside the batch reads nothing and gives NaN outputs.  Asynchronous on `hip_stream`, changes no state.  SO101_ERR_ARG (with a
+ * message): NULL handle or tool, body outside 0..5, non-orthonormal mat, n outside 1 .. 2^26 (or > n_envs when reading the bound state), env_index together
+ * with q, no output.  SO101_ERR_STATE: q == NULL and no state bound. */
+int so101_tool_pose(so101_sim* sim, const so101_tool* tool, const float* q, const int32_t* env_index, int n, float* pos, float* mat, float* jac,
+                    void* hip_stream);
+/* Damped least-squares inverse kinematics, one independent solve per entry: target_pos[n][3], target_mat[n][9] (row-major; may be NULL in mode 0),
+ * q_init[n][6] or NULL = the bound qpos (then env_index as above), q_out[n][6], residual[n][2] = |e_p|, |e_r| at q_out (may be NULL), info[n] = the
+ * iterations used if converged, -1 if not (may be NULL).  The algorithm:
+ *   q = clamp(q_init, q_lo, q_hi)
+ *   for it = 0 .. max_iters:
+ *     p, M, J = tool pose and Jacobian at q;  e_p = p_target - p
+ *     e_r = 0 (mode 0) | rotation vector of the smallest rotation taking M[:,2] to M_target[:,2] (mode 1) | rotation vector of M_target M^T,
+ *           angle in [0, pi] (mode 2)
+ *     if |e_p| <= tol_pos and |e_r| <= tol_rot: info = it, stop;   if it == max_iters: info = -1, stop
+ *     Jr' = 0 (mode 0) | (I - z z^T) Jr, z = M[:,2] (mode 1: the spin about z is left free) | Jr (mode 2)
+ *     Jw = [Jp ; w Jr'], e = [e_p ; w e_r], w = rot_weight
+ *     dq = Jw^T (Jw Jw^T + (e . e + damping) I)^-1 e          (6 x 6 Cholesky without pivoting, in registers)
+ *     if max |dq_j| > max_step: dq *= max_step / max |dq_j|
+ *     q = clamp(q + dq, q_lo, q_hi)
+ * A joint beyond the tool's link has a zero column and keeps clamp(q_init) (for a tool on Fixed_Jaw: the jaw).  A non-finite target gives info = -1 and
+ * q_out = clamp(q_init); an env_index entry outside the batch info = -1 and NaN q_out and residual.  At an angle of exactly pi the rotation axis is
+ * undefined; csrc/so101_tool.hpp says which one is taken.  An entry's output bits depend on its own inputs, the tool and the configuration only - not on the
+ * other entries of the call or on n.  Asynchronous on `hip_stream`, changes no state.  SO101_ERR_ARG as for so101_tool_pose and for: NULL config,
+ * target_pos or q_out, mode outside 0..2, max_iters outside 0..1000, tol_pos / tol_rot / rot_weight / max_step <= 0, damping < 0, q_lo > q_hi, a
+ * missing target_mat in modes 1 and 2.  SO101_ERR_STATE: q_init == NULL and no state bound. */
+int so101_tool_ik(so101_sim* sim, const so101_tool* tool, const so101_ik_config* cfg, const float* target_pos, const float* target_mat,
+                  const float* q_init, const int32_t* env_index, int n, float* q_out, float* residual, int32_t* info, void* hip_stream);
 
 const char* so101_last_error(const so101_sim* sim);
 

@@ -821,6 +821,77 @@ int so101_render(so101_sim* s, const so101_camera* cams, int ncam, int height, i
   return SO101_OK;
 }
 
+// ---- Cartesian tool control (csrc/so101_tool.hpp)
+namespace {
+// the checks so101_tool_pose and so101_tool_ik share: handle state, the tool, the count and where the joints come from.  0 or the status to return.
+int tool_arguments(so101_sim* s, const char* api, const so101_tool* tool, bool has_q, const int32_t* env_index, int n, ToolArg& T) {
+  const std::string a(api);
+  if (!tool) { s->err = a + ": NULL tool"; return SO101_ERR_ARG; }
+  if (tool->body < 0 || tool->body >= NARM) { s->err = a + ": tool body must be 0 .. 5 (an arm link in chain order)"; return SO101_ERR_ARG; }
+  for (int i = 0; i < 3; i++) if (!std::isfinite(tool->pos[i])) { s->err = a + ": tool pos is not finite"; return SO101_ERR_ARG; }
+  for (int i = 0; i < 3; i++)
+    for (int j = 0; j < 3; j++) {
+      double d = 0.0;
+      for (int k = 0; k < 3; k++) d += (double)tool->mat[3 * k + i] * (double)tool->mat[3 * k + j];
+      if (!(std::fabs(d - (i == j ? 1.0 : 0.0)) <= 1e-4)) { s->err = a + ": tool mat is not orthonormal (|M^T M - I| > 1e-4)"; return SO101_ERR_ARG; }
+    }
+  if (n < 1 || n > (1 << 26)) { s->err = a + ": n must be 1 .. 2^26"; return SO101_ERR_ARG; }      // (the kernels index entries with int)
+  if (has_q && env_index) { s->err = a + ": env_index selects envs of the bound state, it cannot be combined with explicit joint angles"; return SO101_ERR_ARG; }
+  if (!has_q) {
+    if (!s->bound) { s->err = a + ": state buffers not bound (call so101_bind_state, or pass the joint angles)"; return SO101_ERR_STATE; }
+    if (!env_index && n > s->n_envs) { s->err = a + ": n exceeds the envs of the handle"; return SO101_ERR_ARG; }
+  }
+  T.body = tool->body;
+  for (int i = 0; i < 3; i++) T.pos[i] = tool->pos[i];
+  for (int i = 0; i < 9; i++) T.mat[i] = tool->mat[i];
+  return SO101_OK;
+}
+}  // namespace
+
+int so101_ik_default_config(const so101_sim* s, so101_ik_config* cfg) {
+  if (!s || !cfg) return SO101_ERR_ARG;
+  memset(cfg, 0, sizeof *cfg);
+  cfg->mode = 1; cfg->max_iters = 60; cfg->tol_pos = 1e-4f; cfg->tol_rot = 1e-3f; cfg->rot_weight = 0.1f; cfg->damping = 1e-6f; cfg->max_step = 0.5f;
+  for (int j = 0; j < NARM; j++) { cfg->q_lo[j] = s->hm.range[j][0]; cfg->q_hi[j] = s->hm.range[j][1]; }
+  return SO101_OK;
+}
+
+int so101_tool_pose(so101_sim* s, const so101_tool* tool, const float* q, const int32_t* env_index, int n, float* pos, float* mat, float* jac, void* stream) {
+  if (!s) return SO101_ERR_ARG;
+  ToolArg T{};
+  if (int rc = tool_arguments(s, "so101_tool_pose", tool, q != nullptr, env_index, n, T)) return rc;
+  if (!pos && !mat && !jac) { s->err = "so101_tool_pose: no output (pos, mat and jac are all NULL)"; return SO101_ERR_ARG; }
+  GUARD_DEVICE(s);
+  so101::launch_tool_pose(n, (hipStream_t)stream, s->dm, T, q, s->buf.qpos, s->n_envs, (const int*)env_index, pos, mat, jac);
+  LAUNCH_CHECK(s, "k_tool_pose");
+  return SO101_OK;
+}
+
+int so101_tool_ik(so101_sim* s, const so101_tool* tool, const so101_ik_config* cfg, const float* target_pos, const float* target_mat, const float* q_init,
+                  const int32_t* env_index, int n, float* q_out, float* residual, int32_t* info, void* stream) {
+  if (!s) return SO101_ERR_ARG;
+  ToolArg T{};
+  if (int rc = tool_arguments(s, "so101_tool_ik", tool, q_init != nullptr, env_index, n, T)) return rc;
+  auto bad = [&](const char* msg) { s->err = std::string("so101_tool_ik: ") + msg; return (int)SO101_ERR_ARG; };
+  if (!cfg) return bad("NULL config");
+  if (!target_pos || !q_out) return bad("target_pos and q_out are required");
+  if (cfg->mode < 0 || cfg->mode > 2) return bad("mode must be 0, 1 or 2");
+  if (cfg->max_iters < 0 || cfg->max_iters > 1000) return bad("max_iters must be 0 .. 1000");
+  if (!(cfg->tol_pos > 0.f) || !(cfg->tol_rot > 0.f) || !(cfg->rot_weight > 0.f) || !(cfg->max_step > 0.f)) return bad("tol_pos, tol_rot, rot_weight and max_step must be positive");
+  if (!(cfg->damping >= 0.f)) return bad("damping must not be negative");
+  for (int j = 0; j < NARM; j++) if (!(cfg->q_lo[j] <= cfg->q_hi[j])) return bad("q_lo must not exceed q_hi");
+  if (cfg->mode != 0 && !target_mat) return bad("modes 1 and 2 need target_mat");
+  IkArg C{};
+  C.mode = cfg->mode; C.max_iters = cfg->max_iters; C.tol_pos = cfg->tol_pos; C.tol_rot = cfg->tol_rot; C.rot_weight = cfg->rot_weight;
+  C.damping = cfg->damping; C.max_step = cfg->max_step;
+  for (int j = 0; j < NARM; j++) { C.q_lo[j] = cfg->q_lo[j]; C.q_hi[j] = cfg->q_hi[j]; }
+  GUARD_DEVICE(s);
+  so101::launch_tool_ik(n, (hipStream_t)stream, s->dm, T, C, target_pos, target_mat, q_init, s->buf.qpos, s->n_envs, (const int*)env_index, q_out, residual,
+                        (int*)info);
+  LAUNCH_CHECK(s, "k_tool_ik");
+  return SO101_OK;
+}
+
 int so101_get_returns(so101_sim* s, float* out, void* stream) {
   REQUIRE_BOUND(s);
   if (!out) return SO101_ERR_ARG;

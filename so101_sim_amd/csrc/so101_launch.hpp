@@ -35,6 +35,12 @@ void launch_render(int n_render, hipStream_t st, const DevModel* m, const StepPa
                    int ncam, int height, int width, const float* planes, const int* plane_adr, float* frames, float* camframes,
                    float* depth, int* seg);
 
+// Cartesian tool control (so101_tool.hpp): lane = env, one wavefront per 64 entries.  q / q_init: [n][6] or NULL = the bound qpos of env env_index[i] (NULL: i)
+void launch_tool_pose(int n, hipStream_t st, const DevModel* m, const ToolArg& T, const float* q, const float* qpos, int n_envs, const int* env_index,
+                      float* pos, float* mat, float* jac);
+void launch_tool_ik(int n, hipStream_t st, const DevModel* m, const ToolArg& T, const IkArg& C, const float* target_pos, const float* target_mat,
+                    const float* q_init, const float* qpos, int n_envs, const int* env_index, float* q_out, float* residual, int* info);
+
 // pipelined step (Newton) -----------------------------------------------------------------------------------------
 void launch_order(hipStream_t st, const unsigned int* cost, int* order, unsigned char* cls, int n_envs, int deal = 1);   // deal: equal slices the sorted envs are dealt to (1 = plain sorted order)
 void launch_pipe_begin(int n_group, hipStream_t st, const DevModel* m, const StepParams& P, const DevBuffers& B, const PrepBuffers& C,

@@ -373,6 +373,120 @@ class BatchedEnvironment:
                         depth.data_ptr(), seg.data_ptr() if seg is not None else None, self._stream())
         return depth, seg
 
+    # ------------------------------------------------------------------ Cartesian tool control (tools.py)
+    def _resolve_tool(self, tool):
+        from . import tools as _tools
+        if getattr(self, "_tools", None) is None:
+            from .model import blob as blobfmt
+            self._tools = _tools.so100_tools(self.meta, blobfmt.unpack(scenes.load_blob(self.task.object_name, "f32")[0]))
+        return _tools.resolve(tool, self._tools)
+
+    def _env_index(self, env_ids):
+        """env_ids (sequence, tensor or None) -> (int32 device tensor or None, count)"""
+        if env_ids is None:
+            return None, self.n_envs
+        torch = self.torch
+        idx = torch.as_tensor(env_ids, dtype=torch.int32, device=self.device).reshape(-1).contiguous()
+        n = int(idx.numel())
+        if n == 0 or int(idx.min()) < 0 or int(idx.max()) >= self.n_envs:
+            raise ValueError("env_ids must name at least one env of this batch")
+        return idx, n
+
+    def _f32(self, a):
+        """array-like or tensor -> float32 tensor on the env's device (numpy input is copied: it may be read-only)"""
+        if isinstance(a, np.ndarray):
+            a = np.array(a, dtype=np.float32)
+        return self.torch.as_tensor(a, dtype=self.torch.float32, device=self.device)
+
+    def _joint_rows(self, q, what):
+        q = self._f32(q)
+        if q.dim() == 1:
+            q = q.unsqueeze(0)
+        if q.dim() != 2 or q.shape[1] != 6 or q.shape[0] < 1:
+            raise ValueError(f"{what} must be [n, 6] joint angles, got {tuple(q.shape)}")
+        return q.contiguous()
+
+    def tool_pose(self, tool="fixed_jaw_pad", env_ids=None, q=None, jacobian: bool = False):
+        """World pose of a tool frame (tools.Tool or a name of the scene's tools) on the GPU (so101_tool_pose): at the current qpos of
+        the envs `env_ids` (None = all), or at explicit joint angles `q` [n, 6].  Returns (pos [n, 3], mat [n, 3, 3]) and, with
+        jacobian=True, jac [n, 6, 6] - rows 0-2 the translational, rows 3-5 the rotational Jacobian of MuJoCo's mj_jacSite."""
+        torch = self.torch
+        t = self._resolve_tool(tool)
+        if q is not None:
+            if env_ids is not None:
+                raise ValueError("env_ids selects envs of the current state: it cannot be combined with q")
+            q = self._joint_rows(q, "q")
+            idx, n = None, int(q.shape[0])
+        else:
+            idx, n = self._env_index(env_ids)
+        pos = torch.empty(n, 3, dtype=torch.float32, device=self.device)
+        mat = torch.empty(n, 3, 3, dtype=torch.float32, device=self.device)
+        jac = torch.empty(n, 6, 6, dtype=torch.float32, device=self.device) if jacobian else None
+        self.sim.tool_pose(t.spec(), q.data_ptr() if q is not None else None, idx.data_ptr() if idx is not None else None, n,
+                           pos.data_ptr(), mat.data_ptr(), jac.data_ptr() if jac is not None else None, self._stream())
+        return (pos, mat, jac) if jacobian else (pos, mat)
+
+    def solve_ik(self, target_pos, target_mat=None, tool="fixed_jaw_pad", mode=None, q_init=None, env_ids=None, **config):
+        """Joint angles that bring a tool to Cartesian targets, one damped least-squares solve per row on the GPU (so101_tool_ik).
+
+        target_pos [n, 3]; target_mat [n, 3, 3] or None.  mode: 0 position only, 1 position and the direction of the tool's z axis,
+        2 position and full orientation; None = 0 without target_mat, else 1.  q_init [n, 6] starts the solves; None starts them
+        from the current qpos of the envs `env_ids` (None = envs 0 .. n - 1).  **config replaces fields of the default settings
+        (max_iters, tol_pos, tol_rot, rot_weight, damping, max_step, q_lo, q_hi; include/so101.h so101_ik_config).
+        Returns (q [n, 6], converged [n] bool, residual [n, 2] = position error in metres and orientation error in radians at q,
+        iters [n] int32, -1 where not converged).  Joints beyond the tool's link keep their starting value."""
+        torch = self.torch
+        t = self._resolve_tool(tool)
+        tp = self._f32(target_pos)
+        if tp.dim() == 1:
+            tp = tp.unsqueeze(0)
+        if tp.dim() != 2 or tp.shape[1] != 3 or tp.shape[0] < 1:
+            raise ValueError(f"target_pos must be [n, 3], got {tuple(tp.shape)}")
+        tp = tp.contiguous()
+        n = int(tp.shape[0])
+        tm = None
+        if target_mat is not None:
+            tm = self._f32(target_mat).reshape(-1, 3, 3).contiguous()
+            if tm.shape[0] != n:
+                raise ValueError(f"target_mat must be [{n}, 3, 3], got {tuple(tm.shape)}")
+        if mode is None:
+            mode = 0 if tm is None else 1
+        if q_init is not None:
+            if env_ids is not None:
+                raise ValueError("env_ids selects envs of the current state: it cannot be combined with q_init")
+            q_init = self._joint_rows(q_init, "q_init")
+            if q_init.shape[0] != n:
+                raise ValueError(f"q_init must be [{n}, 6], got {tuple(q_init.shape)}")
+            idx = None
+        else:
+            idx, k = self._env_index(env_ids)
+            if idx is not None and k != n:
+                raise ValueError(f"env_ids names {k} envs for {n} targets")
+        cfg = self.sim.ik_config(mode=int(mode), **config)
+        q = torch.empty(n, 6, dtype=torch.float32, device=self.device)
+        residual = torch.empty(n, 2, dtype=torch.float32, device=self.device)
+        iters = torch.empty(n, dtype=torch.int32, device=self.device)
+        self.sim.tool_ik(t.spec(), cfg, tp.data_ptr(), tm.data_ptr() if tm is not None else None,
+                         q_init.data_ptr() if q_init is not None else None, idx.data_ptr() if idx is not None else None, n,
+                         q.data_ptr(), residual.data_ptr(), iters.data_ptr(), self._stream())
+        return q, iters >= 0, residual, iters
+
+    def cartesian_action(self, target_pos, target_mat=None, jaw=None, tool="fixed_jaw_pad", mode=None, **config):
+        """An [N, 6] action for step_tensor() that commands the tool of every env to a Cartesian target: the IK solution started
+        from the current qpos (solve_ik), with column 5 replaced by `jaw` (scalar or [N]) when given, minus the configured
+        action_offset - the step computes ctrl = action + offset in float32, so the commanded ctrl is the solution: bit for bit
+        with zero offsets and wherever float32 has an action whose sum with the offset rounds to the solution (the rounded
+        difference is that action: 98.6 % of random joint angles with offsets of a few hundredths), else one unit in the last
+        place beside it.  Targets the solve does not reach still give its last iterate: check solve_ik() where that matters."""
+        torch = self.torch
+        q, _, _, _ = self.solve_ik(target_pos, target_mat, tool=tool, mode=mode, **config)
+        if q.shape[0] != self.n_envs:
+            raise ValueError(f"cartesian_action needs one target per env ({self.n_envs}), got {q.shape[0]}")
+        if jaw is not None:
+            q[:, 5] = self._f32(jaw)
+        offset = torch.tensor([float(x) for x in self.sim.cfg.action_offset], dtype=torch.float32, device=self.device)
+        return q - offset
+
     def events(self, clear: bool = False) -> dict:
         """Counts since creation (or the last clear) of env-steps / env-resets that raised a flag: contact or candidate
         overflow, physics divergence (episode ended like a dm_control PhysicsError), rejected placement, unsettled

@@ -32,7 +32,7 @@ EXPORTS = (
     "so101_version", "so101_max_contacts", "so101_create", "so101_destroy", "so101_default_config",
     "so101_configure", "so101_bind_state", "so101_bind_physics_state", "so101_set_reset_pool", "so101_compute_settled", "so101_set_settled_store", "so101_reset", "so101_settle", "so101_begin_episode", "so101_step", "so101_physics", "so101_reward",
     "so101_get_returns", "so101_get_diag", "so101_get_events", "so101_debug_forward", "so101_debug_candidates", "so101_debug_stages", "so101_get_info", "so101_debug_chain_stats", "so101_last_error",
-    "so101_set_hull_planes", "so101_render",
+    "so101_set_hull_planes", "so101_render", "so101_ik_default_config", "so101_tool_pose", "so101_tool_ik",
     "so101_tree_create", "so101_tree_destroy", "so101_tree_dims", "so101_tree_last_plan", "so101_tree_bind_state", "so101_tree_configure", "so101_tree_physics",
     "so101_tree_debug_forward", "so101_tree_get_diag", "so101_tree_last_error", "so101_tree_obs_dim", "so101_tree_bind_env",
     "so101_tree_configure_env", "so101_tree_bind_physics_state", "so101_tree_reset", "so101_tree_step", "so101_tree_set_hull_planes", "so101_tree_render", "so101_tree_begin_episode", "so101_tree_settle", "so101_tree_compute_settled", "so101_tree_set_settled_store",
@@ -67,6 +67,27 @@ def camera_array(cams):
         arr[k].mat[:] = [float(x) for x in mat]
         arr[k].fovy_deg = float(fovy)
     return arr
+
+
+class ToolSpec(C.Structure):
+    """so101_tool of include/so101.h"""
+    _fields_ = [("body", C.c_int32), ("pos", C.c_float * 3), ("mat", C.c_float * 9)]
+
+
+class IkConfig(C.Structure):
+    """so101_ik_config of include/so101.h"""
+    _fields_ = [("mode", C.c_int32), ("max_iters", C.c_int32), ("tol_pos", C.c_float), ("tol_rot", C.c_float), ("rot_weight", C.c_float),
+                ("damping", C.c_float), ("max_step", C.c_float), ("q_lo", C.c_float * 6), ("q_hi", C.c_float * 6)]
+
+
+def tool_spec(tool) -> ToolSpec:
+    """(body, pos[3], mat[9] row-major) as a so101_tool"""
+    body, pos, mat = tool
+    t = ToolSpec()
+    t.body = int(body)
+    t.pos[:] = [float(x) for x in pos]
+    t.mat[:] = [float(x) for x in mat]
+    return t
 
 
 _libs: dict[str, C.CDLL] = {}
@@ -119,6 +140,9 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.so101_last_error.argtypes = [vp]
     L.so101_set_hull_planes.argtypes = [vp, vp, vp]
     L.so101_render.argtypes = [vp, C.POINTER(CameraSpec), C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp]
+    L.so101_ik_default_config.argtypes = [vp, C.POINTER(IkConfig)]
+    L.so101_tool_pose.argtypes = [vp, C.POINTER(ToolSpec), vp, vp, C.c_int, vp, vp, vp, vp]
+    L.so101_tool_ik.argtypes = [vp, C.POINTER(ToolSpec), C.POINTER(IkConfig), vp, vp, vp, vp, C.c_int, vp, vp, vp, vp]
     _libs[path] = L
     return L
 
@@ -248,6 +272,29 @@ class Sim:
         """cams: sequence of (body, pos[3], mat[9] row-major, fovy_deg); env_index / depth / seg: raw device addresses or None"""
         arr = camera_array(cams)
         self._check(self.L.so101_render(self.h, arr, len(cams), int(height), int(width), env_index, int(n_render), depth, seg, stream), "so101_render")
+
+    def ik_config(self, **kw) -> IkConfig:
+        """so101_ik_default_config (mode 1, 60 iterations, 1e-4 m, 1e-3 rad, the model's joint ranges) with the given fields replaced;
+        q_lo / q_hi take sequences of 6"""
+        cfg = IkConfig()
+        self._check(self.L.so101_ik_default_config(self.h, C.byref(cfg)), "so101_ik_default_config")
+        for k, v in kw.items():
+            if k in ("q_lo", "q_hi"):
+                getattr(cfg, k)[:] = [float(x) for x in v]
+            elif hasattr(cfg, k):
+                setattr(cfg, k, v)
+            else:
+                raise TypeError(f"unknown IK setting {k!r}")
+        return cfg
+
+    def tool_pose(self, tool, q, env_index, n: int, pos, mat, jac, stream=0):
+        """tool: (body, pos[3], mat[9] row-major); q / env_index / pos / mat / jac: raw device addresses or None (so101_tool_pose)"""
+        self._check(self.L.so101_tool_pose(self.h, C.byref(tool_spec(tool)), q, env_index, int(n), pos, mat, jac, stream), "so101_tool_pose")
+
+    def tool_ik(self, tool, cfg: IkConfig, target_pos, target_mat, q_init, env_index, n: int, q_out, residual, info, stream=0):
+        """so101_tool_ik; cfg from ik_config(); the arrays are raw device addresses or None"""
+        self._check(self.L.so101_tool_ik(self.h, C.byref(tool_spec(tool)), C.byref(cfg), target_pos, target_mat, q_init, env_index, int(n),
+                                         q_out, residual, info, stream), "so101_tool_ik")
 
 
 class TreeConfig(C.Structure):
