@@ -239,13 +239,15 @@ int so101_debug_candidates(so101_sim* sim, int32_t* ncand, uint32_t* cand, uint3
  *   SO101_INFO_CHAINS         launch chains of the last pipeline = 1 step
  *   SO101_INFO_HW_QUEUES      GPU_MAX_HW_QUEUES as the library read it (4 when unset)
  *   SO101_INFO_SCHED_ABORTS   times the chained step's watchdog ended a launch (a protocol error; also event 6)
- *   SO101_INFO_SCRATCH_BYTES  library-owned device memory of this handle */
+ *   SO101_INFO_SCRATCH_BYTES  library-owned device memory of this handle
+ *   SO101_INFO_NARROW_LIST_ROWS  1 when the last pipeline = 1 step enqueued the narrowphase with its list row pass (SO101_NARROW_LIST_ROWS) */
 #define SO101_INFO_GRAPH_ACTIVE 0
 #define SO101_INFO_STEP_PATH 1
 #define SO101_INFO_CHAINS 2
 #define SO101_INFO_HW_QUEUES 3
 #define SO101_INFO_SCHED_ABORTS 4
 #define SO101_INFO_SCRATCH_BYTES 5
+#define SO101_INFO_NARROW_LIST_ROWS 6
 long long so101_get_info(so101_sim* sim, int what, void* hip_stream);
 
 /* Where the wavefronts of the chained step's persistent kernel spent their time since the last clear: out = 16 uint64 in

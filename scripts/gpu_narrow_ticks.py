@@ -49,8 +49,14 @@ print("inside the face scan (share of fetch + narrow_pair): face setup %.1f %% |
 
 rp = tk[:, 234:237].astype(np.float64).sum(0)
 if rp[1] > 0:
-    print("row pass (light region, four pairs per wavefront): %.0f rows attempted, %.1f %% settled, %.2f us per pass-row (%.1f ms in all = %.1f %% of fetch + narrow_pair)"
-          % (rp[1], 100 * rp[2] / rp[1], rp[0] * 1e-2 / rp[1], rp[0] * 1e-5, 100 * rp[0] / whole))
+    # (k_narrow<true>: the staged-hull row pass; k_narrow<false> with SO101_NARROW_LIST_ROWS: the list row pass - a handle runs one of the two)
+    which = "list row pass" if s.sim.info().get("narrow_list_rows") == 1 else "row pass"
+    print("%s (light region, four pairs per wavefront): %.0f rows attempted, %.0f settled (%.1f %%), %.2f us per attempted row (%.1f ms in all; fetch + narrow_pair of the full-wave loop: %.1f ms)"
+          % (which, rp[1], rp[2], 100 * rp[2] / rp[1], rp[0] * 1e-2 / rp[1], rp[0] * 1e-5, whole * 1e-5))
+light = [k for k in agg if k in (("table_surface", "container"), ("table_surface", "object"), ("floor", "container"))]
+lt, ln = sum(agg[k][1] for k in light), sum(agg[k][0] for k in light)
+print("the three light classes (table_surface / container, table_surface / object, floor / container): %d candidates (%.1f %%), %.1f ms = %.1f %% of the narrowphase, %.2f us each"
+      % (ln, 100.0 * ln / mask.sum(), lt * 1e-3, 100 * lt / t.sum(), lt / max(ln, 1)))
 
 ex = tk[:, 237:240].astype(np.float64).sum(0)
 print("after the query (share of fetch + narrow_pair): face_patch (five samples -> contacts, wave-uniform arithmetic) %.1f %% | hull-against-hull patches %.1f %%" % (100 * ex[0] / whole, 100 * ex[1] / whole))

@@ -19,6 +19,7 @@ struct G64 {
   DEV static int sub() { return wave_lane(); }
   DEV static void argmax3(float& val, int& idx, float& x, float& y, float& z) { wave_argmax3(val, idx, x, y, z); }
   DEV static void argmax(float& val, int& idx) { wave_argmax(val, idx); }
+  DEV static void argmax_lean(float& val, int& idx) { wave_argmax(val, idx); }
   template <class T> DEV static T ld(const T* p) { return ldc(p); }
   DEV static int uni(int v) { return wave_uniform_i(v); }
 };
@@ -27,6 +28,13 @@ struct G16 {
   DEV static int sub() { return wave_lane() & 15; }
   DEV static void argmax3(float& val, int& idx, float& x, float& y, float& z) { row_argmax3(val, idx, x, y, z); }
   DEV static void argmax(float& val, int& idx) { float x = 0.f, y = 0.f, z = 0.f; row_argmax3(val, idx, x, y, z); }
+  // the payload-free row reduction (wave.hpp row_argmax): same winner.  The list-backed subsets (HullSub) use it for the five patch reductions of
+  // support_multi(); the staged-hull row pass of k_narrow<true> keeps argmax() and with it the code it was measured with.
+#ifdef SO101_EMU      // (the lane-thread emulation brings its own wave primitives and has the payload form only)
+  DEV static void argmax_lean(float& val, int& idx) { argmax(val, idx); }
+#else
+  DEV static void argmax_lean(float& val, int& idx) { row_argmax(val, idx); }
+#endif
   template <class T> DEV static T ld(const T* p) { return *p; }
   DEV static int uni(int v) { return v; }
 };
@@ -163,6 +171,21 @@ template <> struct is_hull_sub<HullSub> { static constexpr bool value = true; };
 DEV void select_hull(bool first, const HullSub& A, const HullSub& B, HullSub& o) {
 #pragma unroll
   for (int j = 0; j < 2; j++) { o.x[j] = first ? A.x[j] : B.x[j]; o.y[j] = first ? A.y[j] : B.y[j]; o.z[j] = first ? A.z[j] : B.z[j]; o.i[j] = first ? A.i[j] : B.i[j]; }
+}
+// The subset of ONE ROW of 16 lanes (policy G16, k_narrow's list row pass): entries sub and sub + 16 of a list of at most HL_ROW_MAX, sub = lane & 15 - in
+// increasing index order per lane like the whole-wave subset; E = the list's first entry (x, y, z, index as bits), cnt = its length (0: every slot empty).
+// The loads are issued together and nothing here waits for them.
+#define HL_ROW_MAX 32
+DEV void hull_sub_row_load(const float* E, int cnt, HullSub& S) {
+  const int sub = wave_lane() & 15;
+#pragma unroll
+  for (int q = 0; q < 2; q++) {
+    int k = sub + 16 * q;
+    bool in = k < cnt;
+    float4 ev; ev.x = 0.f; ev.y = 0.f; ev.z = 0.f; ev.w = 0.f;
+    if (in) ev = *(const float4*)(E + 4 * (size_t)k);
+    S.x[q] = ev.x; S.y[q] = ev.y; S.z[q] = ev.z; S.i[q] = in ? __float_as_int(ev.w) : 0x7fffffff;
+  }
 }
 // cell of the cube map a direction (any length, geom frame) falls into: face 2 a + (negative), then HL_GRID x HL_GRID along the axes a + 1, a + 2
 DEV int hl_cell(const float* dl) {
@@ -853,7 +876,7 @@ DEV void support_multi(const DevModel* m, const GeomW& G, const float (*d)[3], P
   // the five reductions first, then the five winners' coordinates in one burst of loads (fetching each winner right
   // after its reduction put five L2 round trips in series), then the transforms
 #pragma unroll
-  for (int k = 0; k < NCPP; k++) GP::argmax(best[k], bi[k]);
+  for (int k = 0; k < NCPP; k++) { if constexpr (is_hull_sub<Cache>::value) GP::argmax_lean(best[k], bi[k]); else GP::argmax(best[k], bi[k]); }
   float loc[NCPP][3];
 #pragma unroll
   for (int k = 0; k < NCPP; k++) {

@@ -75,7 +75,7 @@ struct so101_sim : HostHandle {      // (so101_host.hpp: device, owned allocatio
   unsigned long long generation = 1, graph_gen = 0;     // bumped by configure / bind_state / set_reset_pool
   bool graph_failed = false;
   hipStream_t graph_failed_stream = nullptr;            // capture is retried when the caller moves to another stream
-  int last_path = -1, last_chains = 0;                  // so101_get_info
+  int last_path = -1, last_chains = 0, last_list_rows = 0;      // so101_get_info
   bool last_graph = false;
   size_t scratch_bytes = 0;
   RenderHost render;                       // cameras (so101_set_hull_planes / so101_render; so101_host.hpp)
@@ -561,17 +561,29 @@ static int enqueue_pipelined(so101_sim* s, hipStream_t st, const so101::StepIO& 
     // (round 6, with the support-bound tables and the fast path for flat faces the light pairs no longer hide a second heavy pair behind the first:
     //  heavy pairs one per fetch and 1.25 wavefronts per env 763 -> 781 k env-steps/s at 4096 envs, 439 -> 461 k at 2048, each alone +1 %; at 8192
     //  envs 893 -> 880 k, so two per fetch and 1.5 wavefronts per env stay there)
-    int ch = chunk_env >= 1 && chunk_env <= NARROW_CHUNK ? chunk_env : (n <= 4096 ? 1 : (n <= 8192 ? 2 : NARROW_CHUNK));
     // (round 5, work items + LDS hull pool of 1024 slots: light pairs per fetch 4 / 3 / 2 / 1 -> 718 / 736 / 740 / 604 k env-steps/s at 4096 envs - four
     //  light pairs with a 512-slot hull among them overflow the pool and stage late -; 32 768 envs, row-pass instance: 4 -> 1078 k, 2 -> 938 k)
-    int cl = chunk_env_l >= 1 && chunk_env_l <= NARROW_CHUNK ? chunk_env_l : (n <= 16 ? 1 : (n <= 8192 ? 2 : NARROW_CHUNK));
     // bit 8: the row pass (four light pairs per wavefront, one per DPP row; so101 tu_narrow.hip).  Measured, round 5: 32 768 envs 996 k -> 1 067 k
     // env-steps/s (first window 1.21 -> 1.35 M); 4096 envs 715 k -> 710 k (there the step follows the critical path of its slowest slice -
     // heavy pairs, long Newton solves -, not the light pairs' instruction count), so it is on above 8192 envs
     const char* rows_var = getenv("SO101_NARROW_ROWS");            // (tests and kernel experiments: read when the step is enqueued / captured, so a handle created after a change sees it)
     const int rows_env = rows_var ? atoi(rows_var) : -1;
     const bool rows = rows_env >= 0 ? rows_env != 0 : n > 8192;
-    W.narrow_chunk = (unsigned int)ch | ((unsigned int)cl << 4) | (rows ? 256u : 0u);        // heavy region | light region | row pass
+    // bit 9: the LIST row pass of the other instance (k_narrow<false>: four list-backed light pairs per wavefront, tu_narrow.hip), read like
+    // SO101_NARROW_ROWS.  A fetch from the light region then takes NARROW_CHUNK pairs: fast items stage no hull, so four of them cannot overflow the pool
+    // (the reason for two per fetch otherwise).
+    const char* lrows_var = getenv("SO101_NARROW_LIST_ROWS");
+    const int lrows_env = lrows_var ? atoi(lrows_var) : -1;
+    // Measured, round 7, env-steps/s, parent library against this one in alternating runs on one machine, three launch chains (profiles/README.md):
+    // 4096 envs 729.0 k -> 749.3 k with the pass and four light pairs per fetch (pass off: 733.4 k); 8192 envs 928.6 k -> 1078.7 k; 2048 envs
+    // 490.9 k -> 455.1 k, so the pass is on above 2048 envs only.  Knobs at 4096 envs with the pass on: light pairs per fetch 4 / 3 / 2 -> 743.9 /
+    // 752.3 / 728.6 k (heavy 1); heavy pairs per fetch 1 / 2 -> 743.9 / 769.8 k (light 4) - with the light chunks four times as fast the launch
+    // again ends on its heavy pairs, and two per fetch halve their atomics -; wavefronts per env 1.0 / 1.25 / 1.5 -> 745.4 / 743.9 / 747.2 k (no difference).
+    const bool list_rows = !rows && (lrows_env >= 0 ? lrows_env != 0 : (SO101_LIST_ROWS_DEFAULT && n > 2048));
+    s->last_list_rows = list_rows ? 1 : 0;
+    int ch = chunk_env >= 1 && chunk_env <= NARROW_CHUNK ? chunk_env : (n <= 4096 ? (list_rows && n > 2048 ? 2 : 1) : (n <= 8192 ? 2 : NARROW_CHUNK));
+    int cl = chunk_env_l >= 1 && chunk_env_l <= NARROW_CHUNK ? chunk_env_l : (list_rows ? NARROW_CHUNK : (n <= 16 ? 1 : (n <= 8192 ? 2 : NARROW_CHUNK)));
+    W.narrow_chunk = (unsigned int)ch | ((unsigned int)cl << 4) | (rows ? 256u : 0u) | (list_rows ? 512u : 0u);        // heavy region | light region | row pass | list row pass
     // persistent narrowphase waves (they pull work items until the list is empty): 1.5 - 2 per env of the slice, at
     // most what fills 256 CUs - a smaller narrowphase grid leaves slots to the other chains' solve kernels
     // (round 4, with the heavy-first work list: 1.5 waves per env 725 k, 2 per env 718 k, 2.5 per env 697 k env-steps/s at 4096 envs)
@@ -748,6 +760,7 @@ long long so101_get_info(so101_sim* s, int what, void* stream) {
     case SO101_INFO_HW_QUEUES: return getenv("SO101_HW_QUEUES_EFFECTIVE") ? atoi(getenv("SO101_HW_QUEUES_EFFECTIVE"))
                                       : (getenv("GPU_MAX_HW_QUEUES") ? atoi(getenv("GPU_MAX_HW_QUEUES")) : 4);
     case SO101_INFO_SCRATCH_BYTES: return (long long)s->scratch_bytes;
+    case SO101_INFO_NARROW_LIST_ROWS: return s->last_list_rows;
     case SO101_INFO_SCHED_ABORTS: {
       DeviceGuard guard(s);
       unsigned int v = 0;

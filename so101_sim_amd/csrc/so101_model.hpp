@@ -263,7 +263,10 @@ struct SolveIO { float* obs; float* reward; float* discount; unsigned char* step
 #ifndef NARROW_CHUNK
 #define NARROW_CHUNK 4     // candidate pairs per narrowphase work item
 #endif
-#define Q_NARROW 0         // queue index = type + class
+#ifndef SO101_LIST_ROWS_DEFAULT
+#define SO101_LIST_ROWS_DEFAULT 1     // k_narrow<false>'s list row pass where SO101_NARROW_LIST_ROWS is unset (so101_hip.hip; measurements: profiles/README.md)
+#endif
+#define Q_NARROW 0        // queue index = type + class
 #define Q_SOLVE 2
 
 // launch parameters of k_chain, kept in device memory (tu_chain.hip)

@@ -178,6 +178,80 @@ __global__ void __launch_bounds__(64, NarrowCfg<ROWS>::waves) k_narrow(const Dev
       }
 #endif
     }
+    // ---- LIST ROW PASS (round 7, this instance only; W.narrow_chunk bit 9): four LIST-BACKED light pairs at once, one per DPP row.  The row pass
+    // above lost at this batch size because a row scanned a whole hull - 16 slots per lane and a trip count of its own per row.  A row here
+    // holds its pair's whole support-vertex list instead, two entries per lane (HullSub, entries sub and sub + 16: lists of up to HL_ROW_MAX),
+    // so every row makes the same two steps per scan and the wave-uniform two thirds of a light pair's instructions are issued once for four
+    // pairs.  A row is attempted when its item names a list (word 47), the list fits the row and the row's own first support direction falls
+    // into the item's cell - the conditions of the full-wave fast path below, which serves every other pair, and every pair the first face does
+    // not settle, exactly as before.  Same entries, same arithmetic, same tie rule (row_argmax3 / row_argmax): same records.
+    if constexpr (!ROWS) if ((W.narrow_chunk & 512u) && i0 >= nheavy && ldc(&m->hl_entry) != nullptr) {
+      unsigned long long tr0 = SO101_CLOCK();
+      const int ln = wave_lane();                      // (taken here: what derives from it lives in this pass only, see wave.hpp)
+#pragma unroll
+      for (int j = 0; j < NARROW_CHUNK; j++) if (ln < ITEM_WORDS) row_items[j * ITEM_WORDS + ln] = it[j];
+      wave_sync();
+      const int row = ln >> 4;
+      const unsigned int* I = row_items + (row < cnt ? row : 0) * ITEM_WORDS;
+      const unsigned int fw = I[47];
+      const int fcnt = (int)(fw & 255u);
+      bool attempt = row < cnt && fw != 0u && fcnt <= HL_ROW_MAX;
+      // the entry loads of all four rows are in flight (one instruction stream: two loads serve every row) while the geoms are unpacked
+      HullSub S1, S2;
+      hull_sub_row_load(ldc(&m->hl_entry) + 4 * (size_t)I[46], attempt ? fcnt : 0, S2);
+#pragma unroll
+      for (int q = 0; q < 2; q++) { S1.x[q] = 0.f; S1.y[q] = 0.f; S1.z[q] = 0.f; S1.i[q] = 0x7fffffff; }
+      bool settled = false;
+      unsigned int ncon = 0u;
+      if (attempt) {
+        GeomW G1, G2;
+        auto geom = [&](int o, GeomW& G) {
+          G.type = (int)I[o + ITEM_G_TYPE]; G.vadr = (int)I[o + ITEM_G_VADR]; G.vnum = (int)I[o + ITEM_G_VNUM];
+#pragma unroll
+          for (int i = 0; i < 3; i++) { G.size[i] = __uint_as_float(I[o + ITEM_G_SIZE + i]); G.p[i] = __uint_as_float(I[o + ITEM_G_P + i]); G.c[i] = __uint_as_float(I[o + ITEM_G_C + i]); }
+#pragma unroll
+          for (int i = 0; i < 9; i++) G.R[i] = __uint_as_float(I[o + ITEM_G_R + i]);
+        };
+        geom(ITEM_GEOM0, G1); geom(ITEM_GEOM1, G2);
+        float rb1 = __uint_as_float(I[ITEM_GEOM0 + ITEM_G_RBOUND]), rb2 = __uint_as_float(I[ITEM_GEOM1 + ITEM_G_RBOUND]);
+        attempt = light_first_cell(G1, G2) == (int)(fw >> 8);
+        if (attempt) {
+          PairContacts pc;
+          settled = narrow_pair_cached<HullSub, G16, true, true>(m, G1, G2, rb1, rb2, S1, S2, pc);
+          if (settled && (ln & 15) == 0) {
+            float* r = W.conres + (size_t)I[0] * CONRES_DIM;
+            r[0] = (float)__popc(pc.valid); r[1] = pc.nrm[0]; r[2] = pc.nrm[1]; r[3] = pc.nrm[2];
+            int o = 4;
+#pragma unroll
+            for (int q = 0; q < NCPP; q++)
+              if ((pc.valid >> q) & 1u) { r[o] = pc.dist[q]; r[o + 1] = pc.pos[q][0]; r[o + 2] = pc.pos[q][1]; r[o + 3] = pc.pos[q][2]; o += 4; }
+          }
+          ncon = (unsigned int)__popc(pc.valid);
+        }
+      }
+      unsigned long long sm = wave_ballot(settled);
+#ifdef SO101_EMU_ROWSTATS
+      { unsigned long long am = wave_ballot(attempt); if (ln == 0) fprintf(stderr, "list row pass: cnt %d attempted mask %llx settled mask %llx i0 %d nheavy %d nwork %d list words %x %x %x %x\n", cnt, am, sm, i0, nheavy, nwork, row_items[47], row_items[ITEM_WORDS + 47], row_items[2 * ITEM_WORDS + 47], row_items[3 * ITEM_WORDS + 47]); }
+#endif
+      todo = 0u;
+#pragma unroll
+      for (int j = 0; j < NARROW_CHUNK; j++) if (j < cnt && !((sm >> (16 * j)) & 1ull)) todo |= 1u << j;
+#ifdef SO101_DEBUG_CLOCKS
+      {          // per-env sums (scripts/gpu_narrow_ticks.py): [10] row-pass ticks, [11] rows attempted, [12] rows settled; a settled pair's own
+                 // slot gets an equal share of the pass (all rows run the one instruction stream)
+        unsigned long long am = wave_ballot(attempt);
+        unsigned int dt = (unsigned int)(SO101_CLOCK() - tr0);
+        int na = __popcll(am) / 16;
+        if (settled && (ln & 15) == 0) W.ticks[I[1]] = ((dt / (unsigned int)(na ? na : 1)) & 0x0fffffffu) | (ncon << 28);
+        if (ln == 0) {
+          unsigned int* rp = W.ticks + (size_t)(item_i(it[0], 1) / MAXCAND) * MAXCAND + 224;
+          atomicAdd(&rp[10], dt); atomicAdd(&rp[11], (unsigned int)na); atomicAdd(&rp[12], (unsigned int)(cnt - __popc(todo)));
+        }
+      }
+#else
+      (void)ncon; (void)tr0;
+#endif
+    }
     wave_sync();
     // not unrolled: four inlined copies of the query are ~130 KB of code, more than the instruction cache holds
 #pragma unroll 1

@@ -186,6 +186,20 @@ __device__ __forceinline__ void row_argmax3(float& val, int& idx, float& x, floa
   row_argmax3_step<DPP_ROW_HALF_MIRROR>(val, idx, x, y, z);
   row_argmax3_step<DPP_ROW_MIRROR>(val, idx, x, y, z);
 }
+// the same reduction without a payload: (value, index) alone, two DPP moves and two selects per step instead of five and five
+template <int CTRL>
+__device__ __forceinline__ void row_argmax_step(float& val, int& idx) {
+  float pv = dpp_f<CTRL>(val);
+  int pi = dpp_i<CTRL>(idx);
+  bool take = pv > val || (pv == val && pi < idx);
+  val = take ? pv : val; idx = take ? pi : idx;
+}
+__device__ __forceinline__ void row_argmax(float& val, int& idx) {
+  row_argmax_step<DPP_QUAD_XOR1>(val, idx);
+  row_argmax_step<DPP_QUAD_XOR2>(val, idx);
+  row_argmax_step<DPP_ROW_HALF_MIRROR>(val, idx);
+  row_argmax_step<DPP_ROW_MIRROR>(val, idx);
+}
 // ---- matrix cores: D (32 x 32, f32) += A (32 x 2) * B (2 x 32), v_mfma_f32_32x32x2_f32.  Lane l supplies A[l % 32][l / 32] and
 // B[l / 32][l % 32]; it holds D[8 (r / 4) + 4 (l / 32) + r % 4][l % 32] in element r of the accumulator.
 typedef float mfma_acc16 __attribute__((ext_vector_type(16)));
