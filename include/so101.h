@@ -35,7 +35,8 @@ extern "C" {
 
 #define SO101_ABI_VERSION 10     /* 10: so101_tree_last_plan, and (additions that change nothing older, so the number stays) the cameras: so101_camera,
                                     so101_set_hull_planes, so101_render, so101_tree_set_hull_planes, so101_tree_render, and Cartesian tool control: so101_tool, so101_ik_config, so101_ik_default_config,
-                                    so101_tool_pose, so101_tool_ik; 9: so101_tree_config gains the observation delays, so101_tree_bind_physics_state; 8: the general-tree engine (so101_tree_*) */
+                                    so101_tool_pose, so101_tool_ik, and the same for the general-tree engine: so101_tree_tool, so101_tree_ik_config, so101_tree_tool_chain,
+                                    so101_tree_ik_default_config, so101_tree_tool_pose, so101_tree_tool_ik; 9: so101_tree_config gains the observation delays, so101_tree_bind_physics_state; 8: the general-tree engine (so101_tree_*) */
 #define SO101_OBS_DIM 18      /* joints_pos(6, delayed) | undelayed_joints_pos(6) | commanded_joints_pos(6) */
 #define SO101_ACT_DIM 6
 #define SO101_SOLVER_PGS 0
@@ -285,7 +286,8 @@ int so101_render(so101_sim* sim, const so101_camera* cams, int ncam, int height,
 /* ---- Cartesian tool control (csrc/so101_tool.hpp): the pose and Jacobian of a frame fixed to an arm link, and the inverse map, for thousands of
  * envs per call on the device.  so101_tool_pose stands in for physics.named.data.site_xpos / site_xmat and mujoco.mj_jacSite of the reference;
  * so101_tool_ik for dm_control's qpos_from_site_pose (dm_control/utils/inverse_kinematics.py), which the reference's data generator approximates by
- * hand (examples/automated_lerobot_dataset_generator.py:180 _inverse_kinematics_approximate).  SO100 engine only so far.  Additions: the ABI number stays. */
+ * hand (examples/automated_lerobot_dataset_generator.py:180 _inverse_kinematics_approximate).  These are the calls of the SO100 engine; the general-tree engine (ALOHA, Dining) has so101_tree_tool_pose /
+ * so101_tree_tool_ik below.  Additions: the ABI number stays. */
 typedef struct {
   int32_t body;       /* 0..5: arm link in chain order, the numbering of so101_camera.body */
   float pos[3];       /* the tool frame in that body's frame */
@@ -439,6 +441,43 @@ int so101_tree_step(so101_tree* sim, const float* action /*[n_envs][nu]*/, float
 int so101_tree_set_hull_planes(so101_tree* sim, const float* planes, const int32_t* plane_adr);
 int so101_tree_render(so101_tree* sim, const so101_camera* cams, int ncam, int height, int width, const int32_t* env_index, int n_render,
                       int source, float* depth, int32_t* seg, void* hip_stream);
+/* ---- Cartesian tool control of this engine (csrc/so101_tree_tool.hpp): so101_tool_pose / so101_tool_ik above for a frame on any articulated body of
+ * a general-tree model - the grippers and fingers of the two ALOHA arms (the sites left/gripper, right/gripper and the four finger sites of
+ * aloha_pbr.xml), on both builds of the engine.  The chain of a tool is the bodies between the world and the tool's body that carry a hinge or slide
+ * joint, root first: ncol <= 8 columns.  Bodies without a joint (the arms' base_link and gripper_base) are folded into fixed transforms on the host.
+ * Additions: the ABI number stays. */
+typedef struct {
+  int32_t body;       /* 1 .. nbody - 1: body id, blob numbering (meta "body_names") */
+  float pos[3];       /* the tool frame in that body's frame */
+  float mat[9];       /* row-major, orthonormal (|M^T M - I| <= 1e-4 entrywise) */
+} so101_tree_tool;
+typedef struct {
+  int32_t mode, max_iters;        /* as so101_ik_config */
+  float tol_pos, tol_rot, rot_weight, damping, max_step;
+  uint32_t free_mask;             /* bit k set: column k of the chain is solved for; clear: its column of Jw is zero and the joint keeps clamp(q_init) */
+  float q_lo[8], q_hi[8];         /* per column; entries at and beyond ncol are ignored */
+} so101_tree_ik_config;
+/* The columns of a tool on `body`: dof[k] (index into qvel), qposadr[k] (index into qpos) and jnt_type[k] (1 hinge, 3 slide), root first; each
+ * array has room for 8 entries and may be NULL.  Returns ncol (1 .. 8), or SO101_ERR_ARG with a message for a body outside 1 .. nbody - 1, a body with
+ * no joint above it (the table), a body whose chain contains a free joint (the props) and a chain longer than 8. */
+int so101_tree_tool_chain(const so101_tree* sim, int body, int32_t* dof, int32_t* qposadr, int32_t* jnt_type);
+/* mode 1, 60 iterations, 1e-4 m, 1e-3 rad, weight 0.1, damping 1e-6, 0.5 per iteration, the model's jnt_range of the chain's joints, free_mask = the
+ * hinge columns (slide joints - the fingers - are held).  Errors as so101_tree_tool_chain. */
+int so101_tree_ik_default_config(const so101_tree* sim, int body, so101_tree_ik_config* cfg);
+/* so101_tool_pose for this engine: pos[n][3], mat[n][9] and jac[n][6][ncol] (row-major; column k belongs to dof[k] of so101_tree_tool_chain: hinge
+ * (a x (p - o), a), slide (a, 0), with a the world axis of the joint and o the world origin of its body).  q: DEVICE [n][ncol] joint values of the
+ * chain, root first, or NULL = the bound qpos ([nq][n_envs]) at the chain's qposadr, of env env_index[i] (NULL: env i, then n <= n_envs).  An env_index
+ * entry outside the batch reads nothing and gives NaN outputs.  Asynchronous on `hip_stream`, changes no state.  SO101_ERR_ARG (with a message) as
+ * for so101_tool_pose and so101_tree_tool_chain; SO101_ERR_STATE: q == NULL and no state bound. */
+int so101_tree_tool_pose(so101_tree* sim, const so101_tree_tool* tool, const float* q, const int32_t* env_index, int n, float* pos, float* mat, float* jac,
+                         void* hip_stream);
+/* so101_tool_ik for this engine - the algorithm written down there, word for word, over ncol columns instead of 6 and with the free_mask: q_init[n][ncol]
+ * or NULL = the bound qpos, q_out[n][ncol], residual[n][2], info[n].  A non-finite target gives info = -1 and q_out = clamp(q_init); an env_index entry
+ * outside the batch info = -1 and NaN q_out and residual.  An entry's output bits depend on its own inputs, the tool and the configuration only - not
+ * on the other entries of the call or on n.  Asynchronous on `hip_stream`, changes no state.  SO101_ERR_ARG as for so101_tree_tool_pose, the checks of
+ * so101_tool_ik on the configuration (q_lo <= q_hi over the chain's columns), and free_mask bits at or above ncol. */
+int so101_tree_tool_ik(so101_tree* sim, const so101_tree_tool* tool, const so101_tree_ik_config* cfg, const float* target_pos, const float* target_mat,
+                       const float* q_init, const int32_t* env_index, int n, float* q_out, float* residual, int32_t* info, void* hip_stream);
 const char* so101_tree_last_error(const so101_tree* sim);
 
 #ifdef __cplusplus

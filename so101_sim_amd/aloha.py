@@ -10,6 +10,8 @@ torch tensors on the GPU with a leading env dimension.
 
 Cameras: `render_depth` casts the scene's six cameras (cameras.ALOHA_CAMERAS) or any cameras.Camera against the collision geometry
 on the GPU (so101_tree_render) - depth and geom ids, from the current or the delayed state; not RGB, and not wired into the observation.
+Cartesian tool control: `tool_pose`, `tool_chain`, `solve_ik` and `cartesian_action` give the pose and Jacobian of the six tool sites
+(tools.ALOHA_TOOLS) or any tools.Tool and the joint values that bring one to a target, batched on the GPU (so101_tree_tool_pose / so101_tree_tool_ik).
 Not built: a non-default table height offset (the committed model blob is compiled for the reference's default).  The observation delays ARE parameters (`joints_observation_delay_secs`, `image_observation_delay_secs`,
 aloha2_task.py:153-159: whole control steps, handed to the kernels by so101_tree_configure_env), and `physics_state` /
 `delayed_physics_state` come from a device-side delay line (so101_tree_bind_physics_state).  Both reward modes are built: the overlap boxes (default) and the contact sequence
@@ -446,6 +448,158 @@ class AlohaEnvironment:
         self.sim.render([c.spec() for c in cams], height, width, idx.data_ptr() if idx is not None else None, n,
                         depth.data_ptr(), seg.data_ptr() if seg is not None else None, self._stream(), source=1 if delayed else 0)
         return depth, seg
+
+    # ------------------------------------------------------------------ Cartesian tool control (tools.py)
+    def _resolve_tool(self, tool):
+        from . import tools as _tools
+        return _tools.resolve(tool, _tools.ALOHA_TOOLS).with_body_ids(self.meta["body_names"])
+
+    def _env_index(self, env_ids):
+        """env_ids (sequence, tensor or None) -> (int32 device tensor or None, count)"""
+        if env_ids is None:
+            return None, self.n_envs
+        torch = self.torch
+        idx = torch.as_tensor(env_ids, dtype=torch.int32, device=self.device).reshape(-1).contiguous()
+        n = int(idx.numel())
+        if n == 0 or int(idx.min()) < 0 or int(idx.max()) >= self.n_envs:
+            raise ValueError("env_ids must name at least one env of this batch")
+        return idx, n
+
+    def _f32(self, a):
+        """array-like or tensor -> float32 tensor on the env's device (numpy input is copied: it may be read-only)"""
+        if isinstance(a, np.ndarray):
+            a = np.array(a, dtype=np.float32)
+        return self.torch.as_tensor(a, dtype=self.torch.float32, device=self.device)
+
+    def _joint_rows(self, q, ncol, what):
+        q = self._f32(q)
+        if q.dim() == 1:
+            q = q.unsqueeze(0)
+        if q.dim() != 2 or q.shape[1] != ncol or q.shape[0] < 1:
+            raise ValueError(f"{what} must be [n, {ncol}] joint values of the tool's chain, got {tuple(q.shape)}")
+        return q.contiguous()
+
+    def tool_chain(self, tool="left/gripper"):
+        """The joints a tool depends on, root first: (dof indices into qvel, qpos addresses, joint types - native.TREE_JNT_HINGE / TREE_JNT_SLIDE).
+        They are the columns of tool_pose's Jacobian and of solve_ik's q."""
+        return self.sim.tool_chain(self._resolve_tool(tool).body)
+
+    def tool_pose(self, tool="left/gripper", env_ids=None, q=None, jacobian: bool = False):
+        """World pose of a tool frame (tools.Tool or a name of tools.ALOHA_TOOLS) on the GPU (so101_tree_tool_pose): at the current qpos of the
+        envs `env_ids` (None = all), or at explicit joint values `q` [n, ncol] of the tool's chain (tool_chain).  Returns (pos [n, 3],
+        mat [n, 3, 3]) and, with jacobian=True, jac [n, 6, ncol] - rows 0-2 the translational, rows 3-5 the rotational Jacobian of MuJoCo's
+        mj_jacSite, column k for dof tool_chain(tool)[0][k]."""
+        torch = self.torch
+        t = self._resolve_tool(tool)
+        ncol = len(self.sim.tool_chain(t.body)[0])
+        if q is not None:
+            if env_ids is not None:
+                raise ValueError("env_ids selects envs of the current state: it cannot be combined with q")
+            q = self._joint_rows(q, ncol, "q")
+            idx, n = None, int(q.shape[0])
+        else:
+            idx, n = self._env_index(env_ids)
+        pos = torch.empty(n, 3, dtype=torch.float32, device=self.device)
+        mat = torch.empty(n, 3, 3, dtype=torch.float32, device=self.device)
+        jac = torch.empty(n, 6, ncol, dtype=torch.float32, device=self.device) if jacobian else None
+        self.sim.tool_pose(t.spec(), q.data_ptr() if q is not None else None, idx.data_ptr() if idx is not None else None, n,
+                           pos.data_ptr(), mat.data_ptr(), jac.data_ptr() if jac is not None else None, self._stream())
+        return (pos, mat, jac) if jacobian else (pos, mat)
+
+    def ik_limits(self, tool="left/gripper"):
+        """Default joint limits of solve_ik for a tool, (lo [ncol], hi [ncol]) float64: the model's jnt_range of the chain's joints, intersected
+        with action_spec() on the actuated arm joints - so the waist stays within the task's waist_joint_limit."""
+        t = self._resolve_tool(tool)
+        dof, _, _ = self.sim.tool_chain(t.body)
+        cfg = self.sim.ik_config(t.body)
+        lo, hi = np.array(cfg.q_lo[:len(dof)], dtype=np.float64), np.array(cfg.q_hi[:len(dof)], dtype=np.float64)
+        spec, cols = self.action_spec(), self._action_columns()
+        for k, d in enumerate(dof):
+            a = cols.get(d)
+            if a is not None:
+                lo[k], hi[k] = max(lo[k], float(spec.minimum[a])), min(hi[k], float(spec.maximum[a]))
+        return lo, hi
+
+    def _action_columns(self):
+        """dof -> action column of the actuated arm joints (the grippers' entries are in follower units, not joint values: left out)"""
+        if getattr(self, "_act_cols", None) is None:
+            m = blobfmt.unpack(self.task.load_blob("f32")[0])
+            grip = np.asarray(m["task_act_is_gripper"]).ravel()
+            self._act_cols = {int(d): a for a, d in enumerate(np.asarray(m["act_dof"]).ravel()) if not int(grip[a])}
+            self._grip_cols = [a for a in range(len(grip)) if int(grip[a])]
+        return self._act_cols
+
+    def solve_ik(self, target_pos, target_mat=None, tool="left/gripper", mode=None, q_init=None, env_ids=None, **config):
+        """Joint values that bring a tool to Cartesian targets, one damped least-squares solve per row on the GPU (so101_tree_tool_ik).
+
+        target_pos [n, 3]; target_mat [n, 3, 3] or None.  mode: 0 position only, 1 position and the direction of the tool's z axis,
+        2 position and full orientation; None = 0 without target_mat, else 1.  q_init [n, ncol] (the tool's chain, tool_chain) starts
+        the solves; None starts them from the current qpos of the envs `env_ids` (None = envs 0 .. n - 1).  **config replaces fields of
+        the default settings (max_iters, tol_pos, tol_rot, rot_weight, damping, max_step, free_mask, q_lo, q_hi; include/so101.h
+        so101_tree_ik_config); the default limits are ik_limits(tool), the default free_mask the hinge columns - a finger's slide joint is held.
+        Returns (q [n, ncol], converged [n] bool, residual [n, 2] = position error in metres and orientation error in radians at q,
+        iters [n] int32, -1 where not converged)."""
+        torch = self.torch
+        t = self._resolve_tool(tool)
+        ncol = len(self.sim.tool_chain(t.body)[0])
+        tp = self._f32(target_pos)
+        if tp.dim() == 1:
+            tp = tp.unsqueeze(0)
+        if tp.dim() != 2 or tp.shape[1] != 3 or tp.shape[0] < 1:
+            raise ValueError(f"target_pos must be [n, 3], got {tuple(tp.shape)}")
+        tp = tp.contiguous()
+        n = int(tp.shape[0])
+        tm = None
+        if target_mat is not None:
+            tm = self._f32(target_mat).reshape(-1, 3, 3).contiguous()
+            if tm.shape[0] != n:
+                raise ValueError(f"target_mat must be [{n}, 3, 3], got {tuple(tm.shape)}")
+        if mode is None:
+            mode = 0 if tm is None else 1
+        if q_init is not None:
+            if env_ids is not None:
+                raise ValueError("env_ids selects envs of the current state: it cannot be combined with q_init")
+            q_init = self._joint_rows(q_init, ncol, "q_init")
+            if q_init.shape[0] != n:
+                raise ValueError(f"q_init must be [{n}, {ncol}], got {tuple(q_init.shape)}")
+            idx = None
+        else:
+            idx, k = self._env_index(env_ids)
+            if idx is not None and k != n:
+                raise ValueError(f"env_ids names {k} envs for {n} targets")
+        lo, hi = self.ik_limits(t)
+        cfg = self.sim.ik_config(t.body, **dict(dict(q_lo=lo, q_hi=hi), mode=int(mode), **config))
+        q = torch.empty(n, ncol, dtype=torch.float32, device=self.device)
+        residual = torch.empty(n, 2, dtype=torch.float32, device=self.device)
+        iters = torch.empty(n, dtype=torch.int32, device=self.device)
+        self.sim.tool_ik(t.spec(), cfg, tp.data_ptr(), tm.data_ptr() if tm is not None else None,
+                         q_init.data_ptr() if q_init is not None else None, idx.data_ptr() if idx is not None else None, n,
+                         q.data_ptr(), residual.data_ptr(), iters.data_ptr(), self._stream())
+        return q, iters >= 0, residual, iters
+
+    def cartesian_action(self, left=None, right=None, gripper_left=None, gripper_right=None, mode=None, **config):
+        """An [N, 14] action for step_tensor() that commands the grippers of every env to Cartesian targets.  `left` / `right`:
+        (target_pos [N, 3], target_mat [N, 3, 3] or None) for the tool "left/gripper" / "right/gripper", solved from the current qpos
+        (solve_ik; mode and **config go there); the solution fills that arm's six entries.  An arm without a target keeps its entries of
+        commanded_joints_pos, a gripper not given (`gripper_left` / `gripper_right`: scalar or [N], the action's follower units) its
+        commanded entry.  The step neither clips nor converts arm entries, so the ctrl commanded for a solved arm IS the solution, bit for
+        bit.  Targets the solve does not reach still give its last iterate: check solve_ik() where that matters."""
+        lo, hi = _SLICES["commanded_joints_pos"]
+        action = self.obs[:, lo:hi].clone()
+        cols = self._action_columns()
+        for name, target in (("left/gripper", left), ("right/gripper", right)):
+            if target is None:
+                continue
+            target_pos, target_mat = target
+            q, _, _, _ = self.solve_ik(target_pos, target_mat, tool=name, mode=mode, **config)
+            if q.shape[0] != self.n_envs:
+                raise ValueError(f"cartesian_action needs one target per env ({self.n_envs}), got {q.shape[0]}")
+            for k, d in enumerate(self.tool_chain(name)[0]):
+                action[:, cols[d]] = q[:, k]
+        for a, g in zip(self._grip_cols, (gripper_left, gripper_right)):
+            if g is not None:
+                action[:, a] = self._f32(g)
+        return action
 
     def episode_returns(self):
         return self.ep_return

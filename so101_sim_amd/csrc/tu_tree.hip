@@ -4,6 +4,7 @@
 #include "so101_host.hpp"
 #include "so101_launch.hpp"
 #include "so101_tree.hpp"
+#include "so101_tree_tool.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -724,6 +725,90 @@ static void launch_tree_prepare(TreeHandle* s, hipStream_t stream) {
   if (hipGetLastError() == hipSuccess && hipEventRecord(s->prep_done, s->prep_stream) == hipSuccess) s->prep_pending = true;
 }
 
+// ---- Cartesian tool control (so101_tree_tool.hpp): the chain of a tool's body, computed per call on the host
+// The bodies from the world down to `body` that carry a hinge or slide joint become the columns, root first; the jointless bodies between them are
+// folded in double precision into the fixed transform in front of the next joint, what lies below the last joint into the tool's frame (pos, mat
+// row-major: identity when `tool` is NULL).  Returns SO101_OK or SO101_ERR_ARG with s->err set; `api` names the caller in the message.
+static int tree_tool_chain(TreeHandle* s, const char* api, int body, const so101_tree_tool* tool, TreeToolArg& T, int* dof /* [8] or NULL */) {
+  const std::string a(api);
+  const TreeModel& M = s->hm;
+  if (body < 1 || body >= M.nbody) { s->err = a + ": tool body must be 1 .. nbody - 1 (a body id of the model)"; return SO101_ERR_ARG; }
+  int path[TB], np = 0, ncol = 0;
+  for (int b = body; b != 0; b = M.body_parent[b]) {
+    path[np++] = b;
+    if (M.body_jnttype[b] == TJ_FREE) { s->err = a + ": the chain of the tool body contains a free joint (a prop, not an arm link)"; return SO101_ERR_ARG; }
+    if (M.body_jnttype[b] == TJ_HINGE || M.body_jnttype[b] == TJ_SLIDE) ncol++;
+  }
+  if (ncol == 0) { s->err = a + ": the tool body has no joint above it (it is fixed to the world)"; return SO101_ERR_ARG; }
+  if (ncol > TREE_TOOL_MAXCOL) { s->err = a + ": the chain of the tool body is longer than 8 joints"; return SO101_ERR_ARG; }
+  auto rot = [](const double* q, const double* v, double* o) {          // o = R(q) v
+    const double w = q[0], x = q[1], y = q[2], z = q[3];
+    const double R[9] = {1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y), 2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x),
+                         2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)};
+    for (int i = 0; i < 3; i++) o[i] = R[3 * i] * v[0] + R[3 * i + 1] * v[1] + R[3 * i + 2] * v[2];
+  };
+  auto mul = [](const double* p, const double* q, double* o) {
+    const double r[4] = {p[0] * q[0] - p[1] * q[1] - p[2] * q[2] - p[3] * q[3], p[0] * q[1] + p[1] * q[0] + p[2] * q[3] - p[3] * q[2],
+                         p[0] * q[2] - p[1] * q[3] + p[2] * q[0] + p[3] * q[1], p[0] * q[3] + p[1] * q[2] - p[2] * q[1] + p[3] * q[0]};
+    for (int i = 0; i < 4; i++) o[i] = r[i];
+  };
+  auto norm = [](double* q) { const double n = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]); for (int i = 0; i < 4; i++) q[i] /= n; };
+  T = TreeToolArg{};
+  double P[3] = {0, 0, 0}, Q[4] = {1, 0, 0, 0};
+  int k = 0;
+  for (int i = np - 1; i >= 0; i--) {
+    const int b = path[i];
+    double bp[3], bq[4], t[3];
+    for (int j = 0; j < 3; j++) bp[j] = M.body_pos[b][j];
+    for (int j = 0; j < 4; j++) bq[j] = M.body_quat[b][j];
+    norm(bq);
+    rot(Q, bp, t);
+    for (int j = 0; j < 3; j++) P[j] += t[j];
+    mul(Q, bq, Q); norm(Q);
+    const int jt = M.body_jnttype[b];
+    if (jt == TJ_HINGE || jt == TJ_SLIDE) {
+      for (int j = 0; j < 3; j++) { T.pos[k][j] = (float)P[j]; T.axis[k][j] = M.jnt_axis[M.body_jnt[b]][j]; }
+      for (int j = 0; j < 4; j++) T.quat[k][j] = (float)Q[j];
+      T.type[k] = jt; T.qposadr[k] = M.body_qposadr[b];
+      if (dof) dof[k] = M.body_dofadr[b];
+      k++;
+      P[0] = P[1] = P[2] = 0.0; Q[0] = 1.0; Q[1] = Q[2] = Q[3] = 0.0;
+    }
+  }
+  T.ncol = ncol;
+  double tp[3] = {0, 0, 0}, tm[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, w[3];
+  if (tool) { for (int j = 0; j < 3; j++) tp[j] = tool->pos[j]; for (int j = 0; j < 9; j++) tm[j] = tool->mat[j]; }
+  rot(Q, tp, w);
+  for (int j = 0; j < 3; j++) T.tpos[j] = (float)(P[j] + w[j]);
+  for (int c = 0; c < 3; c++) {
+    const double col[3] = {tm[c], tm[3 + c], tm[6 + c]};
+    rot(Q, col, w);
+    for (int r = 0; r < 3; r++) T.tmat[3 * r + c] = (float)w[r];
+  }
+  return SO101_OK;
+}
+
+// the checks so101_tree_tool_pose and so101_tree_tool_ik share (those of the SO100 calls): the tool, the count and where the joints come from
+static int tree_tool_arguments(TreeHandle* s, const char* api, const so101_tree_tool* tool, bool has_q, const int32_t* env_index, int n, TreeToolArg& T) {
+  const std::string a(api);
+  if (!tool) { s->err = a + ": NULL tool"; return SO101_ERR_ARG; }
+  for (int i = 0; i < 3; i++) if (!std::isfinite(tool->pos[i])) { s->err = a + ": tool pos is not finite"; return SO101_ERR_ARG; }
+  for (int i = 0; i < 3; i++)
+    for (int j = 0; j < 3; j++) {
+      double d = 0.0;
+      for (int k = 0; k < 3; k++) d += (double)tool->mat[3 * k + i] * (double)tool->mat[3 * k + j];
+      if (!(std::fabs(d - (i == j ? 1.0 : 0.0)) <= 1e-4)) { s->err = a + ": tool mat is not orthonormal (|M^T M - I| > 1e-4)"; return SO101_ERR_ARG; }
+    }
+  if (int rc = tree_tool_chain(s, api, tool->body, tool, T, nullptr)) return rc;
+  if (n < 1 || n > (1 << 26)) { s->err = a + ": n must be 1 .. 2^26"; return SO101_ERR_ARG; }      // (the kernels index entries with int)
+  if (has_q && env_index) { s->err = a + ": env_index selects envs of the bound state, it cannot be combined with explicit joint values"; return SO101_ERR_ARG; }
+  if (!has_q) {
+    if (!s->bound) { s->err = a + ": state buffers not bound (call so101_tree_bind_state, or pass the joint values)"; return SO101_ERR_STATE; }
+    if (!env_index && n > s->n_envs) { s->err = a + ": n exceeds the envs of the handle"; return SO101_ERR_ARG; }
+  }
+  return SO101_OK;
+}
+
 
 extern "C" {
 
@@ -1011,6 +1096,74 @@ int TAPI(render)(TreeHandle* s, const so101_camera* cams, int ncam, int height, 
                      R.frames, R.cams);
   so101::launch_render_image(n_render, (hipStream_t)stream, s->dg, R.frames, R.cams, R.hull_planes, R.plane_adr, ncam, height, width, depth, (int*)seg);
   return hip_ok(s, hipGetLastError(), "k_render") ? SO101_OK : SO101_ERR_HIP;
+}
+
+// ---- Cartesian tool control (so101_tree_tool.hpp)
+int TAPI(tool_chain)(TreeHandle* s, int body, int32_t* dof, int32_t* qposadr, int32_t* jnt_type) {
+  if (!s) return SO101_ERR_ARG;
+  TreeToolArg T{};
+  int d[TREE_TOOL_MAXCOL] = {};
+  if (int rc = tree_tool_chain(s, "so101_tree_tool_chain", body, nullptr, T, d)) return rc;
+  for (int k = 0; k < T.ncol; k++) {
+    if (dof) dof[k] = d[k];
+    if (qposadr) qposadr[k] = T.qposadr[k];
+    if (jnt_type) jnt_type[k] = T.type[k];
+  }
+  return T.ncol;
+}
+
+int TAPI(ik_default_config)(TreeHandle* s, int body, so101_tree_ik_config* cfg) {
+  if (!s || !cfg) return SO101_ERR_ARG;
+  TreeToolArg T{};
+  if (int rc = tree_tool_chain(s, "so101_tree_ik_default_config", body, nullptr, T, nullptr)) return rc;
+  memset(cfg, 0, sizeof *cfg);
+  cfg->mode = 1; cfg->max_iters = 60; cfg->tol_pos = 1e-4f; cfg->tol_rot = 1e-3f; cfg->rot_weight = 0.1f; cfg->damping = 1e-6f; cfg->max_step = 0.5f;
+  int k = T.ncol;
+  for (int b = body; b != 0; b = s->hm.body_parent[b]) {          // the chain's joints, tool side first
+    const int j = s->hm.body_jnt[b];
+    if (j < 0) continue;
+    k--;
+    const bool limited = s->hm.jnt_limited[j] != 0;
+    cfg->q_lo[k] = limited ? s->hm.jnt_range[j][0] : -3.0e38f; cfg->q_hi[k] = limited ? s->hm.jnt_range[j][1] : 3.0e38f;
+    if (T.type[k] == TJ_HINGE) cfg->free_mask |= 1u << k;          // (slide joints - the fingers - are held by default)
+  }
+  return SO101_OK;
+}
+
+int TAPI(tool_pose)(TreeHandle* s, const so101_tree_tool* tool, const float* q, const int32_t* env_index, int n, float* pos, float* mat, float* jac, void* stream) {
+  if (!s) return SO101_ERR_ARG;
+  TreeToolArg T{};
+  if (int rc = tree_tool_arguments(s, "so101_tree_tool_pose", tool, q != nullptr, env_index, n, T)) return rc;
+  if (!pos && !mat && !jac) { s->err = "so101_tree_tool_pose: no output (pos, mat and jac are all NULL)"; return SO101_ERR_ARG; }
+  GUARD_DEVICE(s);
+  hipLaunchKernelGGL(k_tree_tool_pose, dim3((unsigned int)((n + WAVE - 1) / WAVE)), dim3(64), 0, (hipStream_t)stream, T, q, (const float*)s->buf.qpos, s->n_envs,
+                     (const int*)env_index, n, pos, mat, jac);
+  return hip_ok(s, hipGetLastError(), "k_tree_tool_pose") ? SO101_OK : SO101_ERR_HIP;
+}
+
+int TAPI(tool_ik)(TreeHandle* s, const so101_tree_tool* tool, const so101_tree_ik_config* cfg, const float* target_pos, const float* target_mat, const float* q_init,
+                  const int32_t* env_index, int n, float* q_out, float* residual, int32_t* info, void* stream) {
+  if (!s) return SO101_ERR_ARG;
+  TreeToolArg T{};
+  if (int rc = tree_tool_arguments(s, "so101_tree_tool_ik", tool, q_init != nullptr, env_index, n, T)) return rc;
+  auto bad = [&](const char* msg) { s->err = std::string("so101_tree_tool_ik: ") + msg; return (int)SO101_ERR_ARG; };
+  if (!cfg) return bad("NULL config");
+  if (!target_pos || !q_out) return bad("target_pos and q_out are required");
+  if (cfg->mode < 0 || cfg->mode > 2) return bad("mode must be 0, 1 or 2");
+  if (cfg->max_iters < 0 || cfg->max_iters > 1000) return bad("max_iters must be 0 .. 1000");
+  if (!(cfg->tol_pos > 0.f) || !(cfg->tol_rot > 0.f) || !(cfg->rot_weight > 0.f) || !(cfg->max_step > 0.f)) return bad("tol_pos, tol_rot, rot_weight and max_step must be positive");
+  if (!(cfg->damping >= 0.f)) return bad("damping must not be negative");
+  for (int k = 0; k < T.ncol; k++) if (!(cfg->q_lo[k] <= cfg->q_hi[k])) return bad("q_lo must not exceed q_hi");
+  if (T.ncol < 32 && (cfg->free_mask >> T.ncol) != 0u) return bad("free_mask has bits at or above the number of columns of the chain");
+  if (cfg->mode != 0 && !target_mat) return bad("modes 1 and 2 need target_mat");
+  TreeIkArg C{};
+  C.mode = cfg->mode; C.max_iters = cfg->max_iters; C.tol_pos = cfg->tol_pos; C.tol_rot = cfg->tol_rot; C.rot_weight = cfg->rot_weight;
+  C.damping = cfg->damping; C.max_step = cfg->max_step; C.free_mask = cfg->free_mask;
+  for (int k = 0; k < T.ncol; k++) { C.q_lo[k] = cfg->q_lo[k]; C.q_hi[k] = cfg->q_hi[k]; }
+  GUARD_DEVICE(s);
+  hipLaunchKernelGGL(k_tree_tool_ik, dim3((unsigned int)((n + WAVE - 1) / WAVE)), dim3(64), 0, (hipStream_t)stream, T, C, target_pos, target_mat, q_init,
+                     (const float*)s->buf.qpos, s->n_envs, (const int*)env_index, n, q_out, residual, (int*)info);
+  return hip_ok(s, hipGetLastError(), "k_tree_tool_ik") ? SO101_OK : SO101_ERR_HIP;
 }
 
 int TAPI(get_diag)(TreeHandle* s, int* out /* [n_envs][8] device or host-visible memory */, void* stream) {

@@ -29,7 +29,12 @@
   int so101_tree##V##_begin_episode(void*, void*);                                                                                            \
   int so101_tree##V##_step(void*, const float*, float*, float*, float*, uint8_t*, void*);                                                     \
   int so101_tree##V##_set_hull_planes(void*, const float*, const int32_t*);                                                                   \
-  int so101_tree##V##_render(void*, const so101_camera*, int, int, int, const int32_t*, int, int, float*, int32_t*, void*);
+  int so101_tree##V##_render(void*, const so101_camera*, int, int, int, const int32_t*, int, int, float*, int32_t*, void*);                    \
+  int so101_tree##V##_tool_chain(void*, int, int32_t*, int32_t*, int32_t*);                                                                    \
+  int so101_tree##V##_ik_default_config(void*, int, so101_tree_ik_config*);                                                                    \
+  int so101_tree##V##_tool_pose(void*, const so101_tree_tool*, const float*, const int32_t*, int, float*, float*, float*, void*);              \
+  int so101_tree##V##_tool_ik(void*, const so101_tree_tool*, const so101_tree_ik_config*, const float*, const float*, const float*, const int32_t*, int, float*, float*, \
+                              int32_t*, void*);
 
 // (the builds define these with their own handle type in place of void*: same C symbol, same calling convention)
 extern "C" {
@@ -104,6 +109,15 @@ int so101_tree_set_hull_planes(so101_tree* s, const float* planes, const int32_t
 int so101_tree_render(so101_tree* s, const so101_camera* cams, int ncam, int height, int width, const int32_t* env_index, int n_render, int source,
                       float* depth, int32_t* seg, void* stream) {
   return s ? FWD(render, cams, ncam, height, width, env_index, n_render, source, depth, seg, stream) : SO101_ERR_ARG;
+}
+int so101_tree_tool_chain(const so101_tree* s, int body, int32_t* dof, int32_t* qposadr, int32_t* jnt_type) { return s ? FWD(tool_chain, body, dof, qposadr, jnt_type) : SO101_ERR_ARG; }
+int so101_tree_ik_default_config(const so101_tree* s, int body, so101_tree_ik_config* cfg) { return s ? FWD(ik_default_config, body, cfg) : SO101_ERR_ARG; }
+int so101_tree_tool_pose(so101_tree* s, const so101_tree_tool* tool, const float* q, const int32_t* env_index, int n, float* pos, float* mat, float* jac, void* stream) {
+  return s ? FWD(tool_pose, tool, q, env_index, n, pos, mat, jac, stream) : SO101_ERR_ARG;
+}
+int so101_tree_tool_ik(so101_tree* s, const so101_tree_tool* tool, const so101_tree_ik_config* cfg, const float* target_pos, const float* target_mat, const float* q_init,
+                       const int32_t* env_index, int n, float* q_out, float* residual, int32_t* info, void* stream) {
+  return s ? FWD(tool_ik, tool, cfg, target_pos, target_mat, q_init, env_index, n, q_out, residual, info, stream) : SO101_ERR_ARG;
 }
 
 }  // extern "C"

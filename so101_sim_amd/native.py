@@ -36,6 +36,7 @@ EXPORTS = (
     "so101_tree_create", "so101_tree_destroy", "so101_tree_dims", "so101_tree_last_plan", "so101_tree_bind_state", "so101_tree_configure", "so101_tree_physics",
     "so101_tree_debug_forward", "so101_tree_get_diag", "so101_tree_last_error", "so101_tree_obs_dim", "so101_tree_bind_env",
     "so101_tree_configure_env", "so101_tree_bind_physics_state", "so101_tree_reset", "so101_tree_step", "so101_tree_set_hull_planes", "so101_tree_render", "so101_tree_begin_episode", "so101_tree_settle", "so101_tree_compute_settled", "so101_tree_set_settled_store",
+    "so101_tree_tool_chain", "so101_tree_ik_default_config", "so101_tree_tool_pose", "so101_tree_tool_ik",
 )
 
 
@@ -78,6 +79,16 @@ class IkConfig(C.Structure):
     """so101_ik_config of include/so101.h"""
     _fields_ = [("mode", C.c_int32), ("max_iters", C.c_int32), ("tol_pos", C.c_float), ("tol_rot", C.c_float), ("rot_weight", C.c_float),
                 ("damping", C.c_float), ("max_step", C.c_float), ("q_lo", C.c_float * 6), ("q_hi", C.c_float * 6)]
+
+
+class TreeIkConfig(C.Structure):
+    """so101_tree_ik_config of include/so101.h"""
+    _fields_ = [("mode", C.c_int32), ("max_iters", C.c_int32), ("tol_pos", C.c_float), ("tol_rot", C.c_float), ("rot_weight", C.c_float),
+                ("damping", C.c_float), ("max_step", C.c_float), ("free_mask", C.c_uint32), ("q_lo", C.c_float * 8), ("q_hi", C.c_float * 8)]
+
+
+TREE_TOOL_MAXCOL = 8          # columns of a tool's chain at most (so101_tree_tool_chain)
+TREE_JNT_HINGE, TREE_JNT_SLIDE = 1, 3
 
 
 def tool_spec(tool) -> ToolSpec:
@@ -337,6 +348,11 @@ class TreeSim:
         L.so101_tree_set_settled_store.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4
         L.so101_tree_set_hull_planes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.so101_tree_render.argtypes = [C.c_void_p, C.POINTER(CameraSpec), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        vp = C.c_void_p
+        L.so101_tree_tool_chain.argtypes = [vp, C.c_int, vp, vp, vp]
+        L.so101_tree_ik_default_config.argtypes = [vp, C.c_int, C.POINTER(TreeIkConfig)]
+        L.so101_tree_tool_pose.argtypes = [vp, C.POINTER(ToolSpec), vp, vp, C.c_int, vp, vp, vp, vp]
+        L.so101_tree_tool_ik.argtypes = [vp, C.POINTER(ToolSpec), C.POINTER(TreeIkConfig), vp, vp, vp, vp, C.c_int, vp, vp, vp, vp]
         self.n_envs = int(n_envs)
         h = C.c_void_p()
         rc = L.so101_tree_create(blob_f32, len(blob_f32), self.n_envs, int(device), C.byref(h))
@@ -437,3 +453,37 @@ class TreeSim:
         device addresses or None; source 0: the bound qpos, 1: the delayed physics-state line (so101_tree_bind_physics_state)"""
         arr = camera_array(cams)
         self._check(self.L.so101_tree_render(self.h, arr, len(cams), int(height), int(width), env_index, int(n_render), int(source), depth, seg, stream), "so101_tree_render")
+
+    def tool_chain(self, body: int):
+        """The columns of a tool on body `body` (so101_tree_tool_chain): (dof indices, qpos addresses, joint types 1 hinge / 3 slide), root first"""
+        dof, qadr, jt = ((C.c_int32 * TREE_TOOL_MAXCOL)() for _ in range(3))
+        n = self.L.so101_tree_tool_chain(self.h, int(body), dof, qadr, jt)
+        if n < 0:
+            self._check(n, "so101_tree_tool_chain")
+        return list(dof[:n]), list(qadr[:n]), list(jt[:n])
+
+    def ik_config(self, body: int, **kw) -> TreeIkConfig:
+        """so101_tree_ik_default_config for a tool on `body` (mode 1, 60 iterations, 1e-4 m, 1e-3 rad, the chain's joint ranges, the hinge columns
+        free) with the given fields replaced; q_lo / q_hi take one value per column of the chain"""
+        cfg = TreeIkConfig()
+        self._check(self.L.so101_tree_ik_default_config(self.h, int(body), C.byref(cfg)), "so101_tree_ik_default_config")
+        for k, v in kw.items():
+            if k in ("q_lo", "q_hi"):
+                v = [float(x) for x in v]
+                if len(v) > TREE_TOOL_MAXCOL:
+                    raise ValueError(f"{k} takes at most {TREE_TOOL_MAXCOL} values")
+                getattr(cfg, k)[:len(v)] = v
+            elif hasattr(cfg, k):
+                setattr(cfg, k, v)
+            else:
+                raise TypeError(f"unknown IK setting {k!r}")
+        return cfg
+
+    def tool_pose(self, tool, q, env_index, n: int, pos, mat, jac, stream=0):
+        """tool: (body id, pos[3], mat[9] row-major); q / env_index / pos / mat / jac: raw device addresses or None (so101_tree_tool_pose)"""
+        self._check(self.L.so101_tree_tool_pose(self.h, C.byref(tool_spec(tool)), q, env_index, int(n), pos, mat, jac, stream), "so101_tree_tool_pose")
+
+    def tool_ik(self, tool, cfg: TreeIkConfig, target_pos, target_mat, q_init, env_index, n: int, q_out, residual, info, stream=0):
+        """so101_tree_tool_ik; cfg from ik_config(); the arrays are raw device addresses or None"""
+        self._check(self.L.so101_tree_tool_ik(self.h, C.byref(tool_spec(tool)), C.byref(cfg), target_pos, target_mat, q_init, env_index, int(n),
+                                              q_out, residual, info, stream), "so101_tree_tool_ik")
