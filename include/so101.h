@@ -283,7 +283,7 @@ typedef struct {
 int so101_render(so101_sim* sim, const so101_camera* cams, int ncam, int height, int width, const int32_t* env_index, int n_render,
                  float* depth, int32_t* seg, void* hip_stream);
 
-/* ---- Cartesian tool control (csrc/so101_tool.hpp): the pose and Jacobian of a frame fixed to an arm link, and the inverse map, for thousands of
+/* ---- Cartesian tool control (csrc/so101_tool_chain.hpp): the pose and Jacobian of a frame fixed to an arm link, and the inverse map, for thousands of
  * envs per call on the device.  so101_tool_pose stands in for physics.named.data.site_xpos / site_xmat and mujoco.mj_jacSite of the reference;
  * so101_tool_ik for dm_control's qpos_from_site_pose (dm_control/utils/inverse_kinematics.py), which the reference's data generator approximates by
  * hand (examples/automated_lerobot_dataset_generator.py:180 _inverse_kinematics_approximate).  These are the calls of the SO100 engine; the general-tree engine (ALOHA, Dining) has so101_tree_tool_pose /
@@ -331,7 +331,7 @@ int so101_tool_pose(so101_sim* sim, const so101_tool* tool, const float* q, cons
  *     q = clamp(q + dq, q_lo, q_hi)
  * A joint beyond the tool's link has a zero column and keeps clamp(q_init) (for a tool on Fixed_Jaw: the jaw).  A non-finite target gives info = -1 and
  * q_out = clamp(q_init); an env_index entry outside the batch info = -1 and NaN q_out and residual.  At an angle of exactly pi the rotation axis is
- * undefined; csrc/so101_tool.hpp says which one is taken.  An entry's output bits depend on its own inputs, the tool and the configuration only - not on the
+ * undefined; csrc/so101_tool_common.hpp says which one is taken.  An entry's output bits depend on its own inputs, the tool and the configuration only - not on the
  * other entries of the call or on n.  Asynchronous on `hip_stream`, changes no state.  SO101_ERR_ARG as for so101_tool_pose and for: NULL config,
  * target_pos or q_out, mode outside 0..2, max_iters outside 0..1000, tol_pos / tol_rot / rot_weight / max_step <= 0, damping < 0, q_lo > q_hi, a
  * missing target_mat in modes 1 and 2.  SO101_ERR_STATE: q_init == NULL and no state bound. */
@@ -441,7 +441,7 @@ int so101_tree_step(so101_tree* sim, const float* action /*[n_envs][nu]*/, float
 int so101_tree_set_hull_planes(so101_tree* sim, const float* planes, const int32_t* plane_adr);
 int so101_tree_render(so101_tree* sim, const so101_camera* cams, int ncam, int height, int width, const int32_t* env_index, int n_render,
                       int source, float* depth, int32_t* seg, void* hip_stream);
-/* ---- Cartesian tool control of this engine (csrc/so101_tree_tool.hpp): so101_tool_pose / so101_tool_ik above for a frame on any articulated body of
+/* ---- Cartesian tool control of this engine (csrc/so101_tool_chain.hpp): so101_tool_pose / so101_tool_ik above for a frame on any articulated body of
  * a general-tree model - the grippers and fingers of the two ALOHA arms (the sites left/gripper, right/gripper and the four finger sites of
  * aloha_pbr.xml), on both builds of the engine.  The chain of a tool is the bodies between the world and the tool's body that carry a hinge or slide
  * joint, root first: ncol <= 8 columns.  Bodies without a joint (the arms' base_link and gripper_base) are folded into fixed transforms on the host.

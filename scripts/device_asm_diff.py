@@ -9,7 +9,8 @@ translation unit is compiled to gfx950 assembly (--cuda-device-only -S) and comp
 kernel and every out-of-line device function, its .amdhsa_* block, the resource comments behind it (registers, LDS, scratch,
 spills, occupancy) and its entry in the .amdgpu_metadata note.  Allowed to differ: the __hip_cuid_<hash> object (derived from the
 file's path), the order in which symbols appear, and the numbers of assembler-local labels (.LBB<function>_<block>, .Ltmp<n>:
-they count functions in order of appearance).  One line per translation unit and flag set; exit status 1 on any other difference.
+they count functions in order of appearance).  One line per translation unit and flag set (and one for
+a translation unit that only one tree has); exit status 1 on any other difference.
 
 --cache DIR keeps the assembly keyed by a hash of the tree's sources, the flags and the file: the old tree is then compiled once.
 tu_tree.hip alone takes minutes per flag set, which is why this is a script and not a test.
@@ -62,7 +63,7 @@ def assembly(build, src, flags, cache):
 
 _START = re.compile(r"^\s*\.type\s+([^,\s]+),@(function|object)")
 _LEAD = re.compile(r"^\s*\.(globl|protected|weak|hidden|p2align|text|section|local|comm)\b")
-_LOCAL = re.compile(r"\.L[A-Za-z_]+\d+")
+_LOCAL = re.compile(r"\.L[A-Za-z_]+\d+|\bBB\d+(?=_\d)")          # (BB<function>_<block>: the same labels in the loop comments)
 
 
 def symbols(text):
@@ -81,16 +82,24 @@ def symbols(text):
             name, cur = m.group(1), lead
         cur.append(line)
     chunks[name] = cur
+    # (the file's epilogue - padding and the register maximums - follows whichever symbol comes last: a chunk of its own)
+    for name, lines in list(chunks.items()):
+        k = next((i for i, l in enumerate(lines) if ".AMDGPU.gpr_maximums" in l), None)
+        if k is not None:
+            while k > 0 and re.match(r"\s*\.(text|p2alignl|fill)\b", lines[k - 1]):
+                k -= 1
+            chunks[name], chunks["<epilogue>"] = lines[:k], lines[k:]
     out = {}
     for name, lines in chunks.items():
         if name.startswith("__hip_cuid_"):
             continue
         ids = {}
-        norm = [_LOCAL.sub(lambda m: ids.setdefault(m.group(0), ".L%d" % len(ids)), l) for l in lines if l.strip() and "__hip_cuid_" not in l]
+        # (the comment behind a label is aligned to the label's length, which changes with the function's number)
+        norm = [re.sub(r"\s+;", " ;", _LOCAL.sub(lambda m: ids.setdefault(m.group(0), ".L%d" % len(ids)), l)) for l in lines if l.strip() and "__hip_cuid_" not in l]
         out[name] = "\n".join(norm)
     entry = []
     for line in note.splitlines() + ["  - end"]:
-        if line.startswith("  - ") and entry:
+        if (line.startswith("  - ") or line.startswith("amdhsa.")) and entry:          # (amdhsa.target / amdhsa.version close the note, behind the last kernel)
             m = re.search(r"^\s+\.name:\s+(\S+)", "\n".join(entry), re.M)
             out["<metadata> " + (m.group(1) if m else entry[0])] = "\n".join(entry)
             entry = []
@@ -110,10 +119,10 @@ def main():
     trees = [os.path.abspath(a.old), os.path.abspath(a.new)]
     builds = [load_build(t) for t in trees]
     names = [sorted(os.path.basename(p) for p in b.translation_units() if fnmatch.fnmatch(os.path.basename(p), a.only)) for b in builds]
-    if names[0] != names[1]:
-        print("translation units differ: %s" % sorted(set(names[0]) ^ set(names[1])))
-        return 1
-    jobs = [(tu, v, kw) for v, kw in VARIANTS if v in a.variants.split(",") for tu in names[0]]
+    only = sorted(set(names[0]) ^ set(names[1]))          # a translation unit added or removed: reported, the others are compared
+    for tu in only:
+        print("%-22s only in the %s tree" % (tu, "old" if tu in names[0] else "new"), flush=True)
+    jobs = [(tu, v, kw) for v, kw in VARIANTS if v in a.variants.split(",") for tu in sorted(set(names[0]) & set(names[1]))]
     jobs.sort(key=lambda j: not j[0].startswith(SLOW_FIRST))
 
     def one(job):
@@ -131,7 +140,7 @@ def main():
             else:
                 print("%-22s %-13s identical (%d symbols)" % (tu, v, nfun), flush=True)
     print("%d of %d compilations differ" % (bad, len(jobs)))
-    return 1 if bad else 0
+    return 1 if bad or only else 0
 
 
 if __name__ == "__main__":

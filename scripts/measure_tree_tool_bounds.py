@@ -2,7 +2,7 @@
 
     python scripts/measure_tree_tool_bounds.py [--states 2000]
 
-A float32 numpy evaluation of the chain formulas of csrc/so101_tree_tool.hpp - the host's fold of the jointless bodies in double precision,
+A float32 numpy evaluation of the chain formulas of csrc/so101_tool_chain.hpp - the host's fold of the jointless bodies in double precision,
 then per column xp += R pos, xq = xq * quat, hinge xq = xq * (cos q/2, axis sin q/2), normquat, slide xp += rot(axis, xq) q, and the Jacobian
 columns - on random joint values within the default limits, for the four tools of tests/tree_tool_cases.py on the ALOHA blob, against the fp64
 reference of tests/tree_tool_ref.py.  It runs on the CPU and does not touch the kernels under test.  Prints the worst differences in position

@@ -28,6 +28,7 @@ from . import native
 from ._dmenv import Array, BoundedArray, TimeStep
 from .model import blob as blobfmt
 from .model import scenes
+from .tool_control import ToolControl
 
 DEFAULT_CONTROL_TIMESTEP = 0.02
 PHYSICS_TIMESTEP = 0.002
@@ -132,7 +133,7 @@ def aloha_action_spec(ctrlrange: np.ndarray, waist_joint_limit: float = np.pi / 
     return BoundedArray((14,), np.float32, lo, hi)
 
 
-class AlohaEnvironment:
+class AlohaEnvironment(ToolControl):
     def __init__(self, task: HandOverTask, n_envs: int = 1, time_limit: float = float("inf"), random_state=None, device=None,
                  env_id_base: int = 0, solver_iterations: int = 0, solver_tolerance: float = -1.0, settle_max_substeps: int = 1000,
                  physics_state: bool | None = None, seed_compatible: bool = True, narrowphase: str = "epa", prefetch_resets: bool = True, pipeline: bool = True):
@@ -437,12 +438,7 @@ class AlohaEnvironment:
         if delayed and not self._with_state:
             raise ValueError("render_depth(delayed=True) needs the physics-state delay line: create the environment with physics_state=True")
         self._ensure_hull_planes()
-        idx, n = None, self.n_envs
-        if env_ids is not None:
-            idx = torch.as_tensor(env_ids, dtype=torch.int32, device=self.device).reshape(-1).contiguous()
-            n = int(idx.numel())
-            if n == 0 or int(idx.min()) < 0 or int(idx.max()) >= self.n_envs:
-                raise ValueError("env_ids must name at least one env of this batch")
+        idx, n = self._env_index(env_ids)
         depth = torch.empty(n, len(cams), int(height), int(width), dtype=torch.float32, device=self.device)
         seg = torch.empty(n, len(cams), int(height), int(width), dtype=torch.int32, device=self.device) if segmentation else None
         self.sim.render([c.spec() for c in cams], height, width, idx.data_ptr() if idx is not None else None, n,
@@ -454,30 +450,12 @@ class AlohaEnvironment:
         from . import tools as _tools
         return _tools.resolve(tool, _tools.ALOHA_TOOLS).with_body_ids(self.meta["body_names"])
 
-    def _env_index(self, env_ids):
-        """env_ids (sequence, tensor or None) -> (int32 device tensor or None, count)"""
-        if env_ids is None:
-            return None, self.n_envs
-        torch = self.torch
-        idx = torch.as_tensor(env_ids, dtype=torch.int32, device=self.device).reshape(-1).contiguous()
-        n = int(idx.numel())
-        if n == 0 or int(idx.min()) < 0 or int(idx.max()) >= self.n_envs:
-            raise ValueError("env_ids must name at least one env of this batch")
-        return idx, n
+    def _tool_columns(self, t):
+        return len(self.sim.tool_chain(t.body)[0])
 
-    def _f32(self, a):
-        """array-like or tensor -> float32 tensor on the env's device (numpy input is copied: it may be read-only)"""
-        if isinstance(a, np.ndarray):
-            a = np.array(a, dtype=np.float32)
-        return self.torch.as_tensor(a, dtype=self.torch.float32, device=self.device)
-
-    def _joint_rows(self, q, ncol, what):
-        q = self._f32(q)
-        if q.dim() == 1:
-            q = q.unsqueeze(0)
-        if q.dim() != 2 or q.shape[1] != ncol or q.shape[0] < 1:
-            raise ValueError(f"{what} must be [n, {ncol}] joint values of the tool's chain, got {tuple(q.shape)}")
-        return q.contiguous()
+    def _ik_config(self, t, mode, config):
+        lo, hi = self.ik_limits(t)
+        return self.sim.ik_config(t.body, **dict(dict(q_lo=lo, q_hi=hi), mode=mode, **config))
 
     def tool_chain(self, tool="left/gripper"):
         """The joints a tool depends on, root first: (dof indices into qvel, qpos addresses, joint types - native.TREE_JNT_HINGE / TREE_JNT_SLIDE).
@@ -489,22 +467,7 @@ class AlohaEnvironment:
         envs `env_ids` (None = all), or at explicit joint values `q` [n, ncol] of the tool's chain (tool_chain).  Returns (pos [n, 3],
         mat [n, 3, 3]) and, with jacobian=True, jac [n, 6, ncol] - rows 0-2 the translational, rows 3-5 the rotational Jacobian of MuJoCo's
         mj_jacSite, column k for dof tool_chain(tool)[0][k]."""
-        torch = self.torch
-        t = self._resolve_tool(tool)
-        ncol = len(self.sim.tool_chain(t.body)[0])
-        if q is not None:
-            if env_ids is not None:
-                raise ValueError("env_ids selects envs of the current state: it cannot be combined with q")
-            q = self._joint_rows(q, ncol, "q")
-            idx, n = None, int(q.shape[0])
-        else:
-            idx, n = self._env_index(env_ids)
-        pos = torch.empty(n, 3, dtype=torch.float32, device=self.device)
-        mat = torch.empty(n, 3, 3, dtype=torch.float32, device=self.device)
-        jac = torch.empty(n, 6, ncol, dtype=torch.float32, device=self.device) if jacobian else None
-        self.sim.tool_pose(t.spec(), q.data_ptr() if q is not None else None, idx.data_ptr() if idx is not None else None, n,
-                           pos.data_ptr(), mat.data_ptr(), jac.data_ptr() if jac is not None else None, self._stream())
-        return (pos, mat, jac) if jacobian else (pos, mat)
+        return self._tool_pose(tool, env_ids, q, jacobian)
 
     def ik_limits(self, tool="left/gripper"):
         """Default joint limits of solve_ik for a tool, (lo [ncol], hi [ncol]) float64: the model's jnt_range of the chain's joints, intersected
@@ -539,43 +502,7 @@ class AlohaEnvironment:
         so101_tree_ik_config); the default limits are ik_limits(tool), the default free_mask the hinge columns - a finger's slide joint is held.
         Returns (q [n, ncol], converged [n] bool, residual [n, 2] = position error in metres and orientation error in radians at q,
         iters [n] int32, -1 where not converged)."""
-        torch = self.torch
-        t = self._resolve_tool(tool)
-        ncol = len(self.sim.tool_chain(t.body)[0])
-        tp = self._f32(target_pos)
-        if tp.dim() == 1:
-            tp = tp.unsqueeze(0)
-        if tp.dim() != 2 or tp.shape[1] != 3 or tp.shape[0] < 1:
-            raise ValueError(f"target_pos must be [n, 3], got {tuple(tp.shape)}")
-        tp = tp.contiguous()
-        n = int(tp.shape[0])
-        tm = None
-        if target_mat is not None:
-            tm = self._f32(target_mat).reshape(-1, 3, 3).contiguous()
-            if tm.shape[0] != n:
-                raise ValueError(f"target_mat must be [{n}, 3, 3], got {tuple(tm.shape)}")
-        if mode is None:
-            mode = 0 if tm is None else 1
-        if q_init is not None:
-            if env_ids is not None:
-                raise ValueError("env_ids selects envs of the current state: it cannot be combined with q_init")
-            q_init = self._joint_rows(q_init, ncol, "q_init")
-            if q_init.shape[0] != n:
-                raise ValueError(f"q_init must be [{n}, {ncol}], got {tuple(q_init.shape)}")
-            idx = None
-        else:
-            idx, k = self._env_index(env_ids)
-            if idx is not None and k != n:
-                raise ValueError(f"env_ids names {k} envs for {n} targets")
-        lo, hi = self.ik_limits(t)
-        cfg = self.sim.ik_config(t.body, **dict(dict(q_lo=lo, q_hi=hi), mode=int(mode), **config))
-        q = torch.empty(n, ncol, dtype=torch.float32, device=self.device)
-        residual = torch.empty(n, 2, dtype=torch.float32, device=self.device)
-        iters = torch.empty(n, dtype=torch.int32, device=self.device)
-        self.sim.tool_ik(t.spec(), cfg, tp.data_ptr(), tm.data_ptr() if tm is not None else None,
-                         q_init.data_ptr() if q_init is not None else None, idx.data_ptr() if idx is not None else None, n,
-                         q.data_ptr(), residual.data_ptr(), iters.data_ptr(), self._stream())
-        return q, iters >= 0, residual, iters
+        return self._solve_ik(target_pos, target_mat, tool, mode, q_init, env_ids, config)
 
     def cartesian_action(self, left=None, right=None, gripper_left=None, gripper_right=None, mode=None, **config):
         """An [N, 14] action for step_tensor() that commands the grippers of every env to Cartesian targets.  `left` / `right`:

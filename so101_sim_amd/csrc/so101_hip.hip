@@ -834,48 +834,42 @@ int so101_render(so101_sim* s, const so101_camera* cams, int ncam, int height, i
   return SO101_OK;
 }
 
-// ---- Cartesian tool control (csrc/so101_tool.hpp)
+// ---- Cartesian tool control (csrc/so101_tool_chain.hpp)
 namespace {
-// the checks so101_tool_pose and so101_tool_ik share: handle state, the tool, the count and where the joints come from.  0 or the status to return.
-int tool_arguments(so101_sim* s, const char* api, const so101_tool* tool, bool has_q, const int32_t* env_index, int n, ToolArg& T) {
-  const std::string a(api);
-  if (!tool) { s->err = a + ": NULL tool"; return SO101_ERR_ARG; }
-  if (tool->body < 0 || tool->body >= NARM) { s->err = a + ": tool body must be 0 .. 5 (an arm link in chain order)"; return SO101_ERR_ARG; }
-  for (int i = 0; i < 3; i++) if (!std::isfinite(tool->pos[i])) { s->err = a + ": tool pos is not finite"; return SO101_ERR_ARG; }
-  for (int i = 0; i < 3; i++)
-    for (int j = 0; j < 3; j++) {
-      double d = 0.0;
-      for (int k = 0; k < 3; k++) d += (double)tool->mat[3 * k + i] * (double)tool->mat[3 * k + j];
-      if (!(std::fabs(d - (i == j ? 1.0 : 0.0)) <= 1e-4)) { s->err = a + ": tool mat is not orthonormal (|M^T M - I| > 1e-4)"; return SO101_ERR_ARG; }
-    }
-  if (n < 1 || n > (1 << 26)) { s->err = a + ": n must be 1 .. 2^26"; return SO101_ERR_ARG; }      // (the kernels index entries with int)
-  if (has_q && env_index) { s->err = a + ": env_index selects envs of the bound state, it cannot be combined with explicit joint angles"; return SO101_ERR_ARG; }
-  if (!has_q) {
-    if (!s->bound) { s->err = a + ": state buffers not bound (call so101_bind_state, or pass the joint angles)"; return SO101_ERR_STATE; }
-    if (!env_index && n > s->n_envs) { s->err = a + ": n exceeds the envs of the handle"; return SO101_ERR_ARG; }
+// The chain of a tool on an arm link: the base as the root, one hinge column per arm link up to the tool's; the links beyond it are I/O columns
+// only.  0 or the status to return, with s->err set.
+int so100_tool_chain(so101_sim* s, const char* api, const so101_tool* tool, ToolChain<NARM>& T) {
+  if (int rc = check_tool_frame(s, api, tool)) return rc;
+  if (tool->body < 0 || tool->body >= NARM) { s->err = std::string(api) + ": tool body must be 0 .. 5 (an arm link in chain order)"; return SO101_ERR_ARG; }
+  const DevModel& M = s->hm;
+  T = ToolChain<NARM>{};
+  T.ncol = tool->body + 1; T.nio = NARM;
+  memcpy(T.rpos, M.base_pos, sizeof T.rpos); memcpy(T.rquat, M.base_quat, sizeof T.rquat);
+  for (int k = 0; k < NARM; k++) {
+    T.type[k] = TOOL_HINGE; T.qposadr[k] = k;
+    if (k >= T.ncol) continue;
+    memcpy(T.pos[k], M.arm_pos[k], sizeof T.pos[k]); memcpy(T.quat[k], M.arm_quat[k], sizeof T.quat[k]); memcpy(T.axis[k], M.arm_axis[k], sizeof T.axis[k]);
   }
-  T.body = tool->body;
-  for (int i = 0; i < 3; i++) T.pos[i] = tool->pos[i];
-  for (int i = 0; i < 9; i++) T.mat[i] = tool->mat[i];
+  memcpy(T.tpos, tool->pos, sizeof T.tpos); memcpy(T.tmat, tool->mat, sizeof T.tmat);
   return SO101_OK;
 }
 }  // namespace
 
 int so101_ik_default_config(const so101_sim* s, so101_ik_config* cfg) {
   if (!s || !cfg) return SO101_ERR_ARG;
-  memset(cfg, 0, sizeof *cfg);
-  cfg->mode = 1; cfg->max_iters = 60; cfg->tol_pos = 1e-4f; cfg->tol_rot = 1e-3f; cfg->rot_weight = 0.1f; cfg->damping = 1e-6f; cfg->max_step = 0.5f;
+  ik_default_settings(cfg);
   for (int j = 0; j < NARM; j++) { cfg->q_lo[j] = s->hm.range[j][0]; cfg->q_hi[j] = s->hm.range[j][1]; }
   return SO101_OK;
 }
 
 int so101_tool_pose(so101_sim* s, const so101_tool* tool, const float* q, const int32_t* env_index, int n, float* pos, float* mat, float* jac, void* stream) {
   if (!s) return SO101_ERR_ARG;
-  ToolArg T{};
-  if (int rc = tool_arguments(s, "so101_tool_pose", tool, q != nullptr, env_index, n, T)) return rc;
+  ToolChain<NARM> T;
+  if (int rc = so100_tool_chain(s, "so101_tool_pose", tool, T)) return rc;
+  if (int rc = check_tool_entries(s, "so101_tool_pose", q != nullptr, env_index != nullptr, n, s->bound, s->n_envs)) return rc;
   if (!pos && !mat && !jac) { s->err = "so101_tool_pose: no output (pos, mat and jac are all NULL)"; return SO101_ERR_ARG; }
   GUARD_DEVICE(s);
-  so101::launch_tool_pose(n, (hipStream_t)stream, s->dm, T, q, s->buf.qpos, s->n_envs, (const int*)env_index, pos, mat, jac);
+  so101::launch_tool_pose(n, (hipStream_t)stream, T, q, s->buf.qpos, s->n_envs, (const int*)env_index, pos, mat, jac);
   LAUNCH_CHECK(s, "k_tool_pose");
   return SO101_OK;
 }
@@ -883,24 +877,13 @@ int so101_tool_pose(so101_sim* s, const so101_tool* tool, const float* q, const 
 int so101_tool_ik(so101_sim* s, const so101_tool* tool, const so101_ik_config* cfg, const float* target_pos, const float* target_mat, const float* q_init,
                   const int32_t* env_index, int n, float* q_out, float* residual, int32_t* info, void* stream) {
   if (!s) return SO101_ERR_ARG;
-  ToolArg T{};
-  if (int rc = tool_arguments(s, "so101_tool_ik", tool, q_init != nullptr, env_index, n, T)) return rc;
-  auto bad = [&](const char* msg) { s->err = std::string("so101_tool_ik: ") + msg; return (int)SO101_ERR_ARG; };
-  if (!cfg) return bad("NULL config");
-  if (!target_pos || !q_out) return bad("target_pos and q_out are required");
-  if (cfg->mode < 0 || cfg->mode > 2) return bad("mode must be 0, 1 or 2");
-  if (cfg->max_iters < 0 || cfg->max_iters > 1000) return bad("max_iters must be 0 .. 1000");
-  if (!(cfg->tol_pos > 0.f) || !(cfg->tol_rot > 0.f) || !(cfg->rot_weight > 0.f) || !(cfg->max_step > 0.f)) return bad("tol_pos, tol_rot, rot_weight and max_step must be positive");
-  if (!(cfg->damping >= 0.f)) return bad("damping must not be negative");
-  for (int j = 0; j < NARM; j++) if (!(cfg->q_lo[j] <= cfg->q_hi[j])) return bad("q_lo must not exceed q_hi");
-  if (cfg->mode != 0 && !target_mat) return bad("modes 1 and 2 need target_mat");
-  IkArg C{};
-  C.mode = cfg->mode; C.max_iters = cfg->max_iters; C.tol_pos = cfg->tol_pos; C.tol_rot = cfg->tol_rot; C.rot_weight = cfg->rot_weight;
-  C.damping = cfg->damping; C.max_step = cfg->max_step;
-  for (int j = 0; j < NARM; j++) { C.q_lo[j] = cfg->q_lo[j]; C.q_hi[j] = cfg->q_hi[j]; }
+  ToolChain<NARM> T;
+  IkSettings<NARM> C;
+  if (int rc = so100_tool_chain(s, "so101_tool_ik", tool, T)) return rc;
+  if (int rc = check_tool_entries(s, "so101_tool_ik", q_init != nullptr, env_index != nullptr, n, s->bound, s->n_envs)) return rc;
+  if (int rc = ik_settings(s, "so101_tool_ik", cfg, NARM, (1u << NARM) - 1u, target_pos != nullptr, target_mat != nullptr, q_out != nullptr, C)) return rc;
   GUARD_DEVICE(s);
-  so101::launch_tool_ik(n, (hipStream_t)stream, s->dm, T, C, target_pos, target_mat, q_init, s->buf.qpos, s->n_envs, (const int*)env_index, q_out, residual,
-                        (int*)info);
+  so101::launch_tool_ik(n, (hipStream_t)stream, T, C, target_pos, target_mat, q_init, s->buf.qpos, s->n_envs, (const int*)env_index, q_out, residual, (int*)info);
   LAUNCH_CHECK(s, "k_tool_ik");
   return SO101_OK;
 }

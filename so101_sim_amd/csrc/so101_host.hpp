@@ -7,6 +7,7 @@
 #include "so101_blob.hpp"
 #include "../../include/so101.h"
 #include "so101_tables.hpp"
+#include "so101_tool_chain.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -215,4 +216,63 @@ inline bool render_arguments(HostHandle* s, const char* api, const so101_camera*
     memcpy(rc.cam[k].pos, cams[k].pos, sizeof rc.cam[k].pos); memcpy(rc.cam[k].mat, cams[k].mat, sizeof rc.cam[k].mat);
   }
   return true;
+}
+
+// ---------------------------------------------------------------------------------------------------- Cartesian tool control
+// What the tool calls of both engines check before they build their chain and launch (so101_tool_chain.hpp).  Each returns SO101_OK or the
+// status to return with "<api>: <what>" in s->err.  Tool: so101_tool / so101_tree_tool; Cfg: so101_ik_config / so101_tree_ik_config.
+
+// the tool is there, its frame finite and orthonormal (the body is the engine's to check)
+template <typename Tool>
+int check_tool_frame(HostHandle* s, const char* api, const Tool* tool) {
+  const std::string a(api);
+  if (!tool) { s->err = a + ": NULL tool"; return SO101_ERR_ARG; }
+  for (int i = 0; i < 3; i++) if (!std::isfinite(tool->pos[i])) { s->err = a + ": tool pos is not finite"; return SO101_ERR_ARG; }
+  for (int i = 0; i < 3; i++)
+    for (int j = 0; j < 3; j++) {
+      double d = 0.0;
+      for (int k = 0; k < 3; k++) d += (double)tool->mat[3 * k + i] * (double)tool->mat[3 * k + j];
+      if (!(std::fabs(d - (i == j ? 1.0 : 0.0)) <= 1e-4)) { s->err = a + ": tool mat is not orthonormal (|M^T M - I| > 1e-4)"; return SO101_ERR_ARG; }
+    }
+  return SO101_OK;
+}
+
+// the count and where the joints come from: explicit values (has_q) or the handle's bound state, all of it or the envs of env_index
+inline int check_tool_entries(HostHandle* s, const char* api, bool has_q, bool has_index, int n, bool bound, int n_envs) {
+  const std::string a(api);
+  if (n < 1 || n > (1 << 26)) { s->err = a + ": n must be 1 .. 2^26"; return SO101_ERR_ARG; }      // (the kernels index entries with int)
+  if (has_q && has_index) { s->err = a + ": env_index selects envs of the bound state, it cannot be combined with explicit joint values"; return SO101_ERR_ARG; }
+  if (!has_q) {
+    if (!bound) { s->err = a + ": state buffers not bound (bind the state first, or pass the joint values)"; return SO101_ERR_STATE; }
+    if (!has_index && n > n_envs) { s->err = a + ": n exceeds the envs of the handle"; return SO101_ERR_ARG; }
+  }
+  return SO101_OK;
+}
+
+// the settings every default config starts from (include/so101.h); the limits - and the tree engine's free_mask - are the engine's to add
+template <typename Cfg>
+void ik_default_settings(Cfg* cfg) {
+  memset(cfg, 0, sizeof *cfg);
+  cfg->mode = 1; cfg->max_iters = 60; cfg->tol_pos = 1e-4f; cfg->tol_rot = 1e-3f; cfg->rot_weight = 0.1f; cfg->damping = 1e-6f; cfg->max_step = 0.5f;
+}
+
+// the fields of a config and the arrays an IK call cannot do without, checked over the nio columns the call reads, into the kernel argument
+template <int NC, typename Cfg>
+int ik_settings(HostHandle* s, const char* api, const Cfg* cfg, int nio, unsigned int free_mask, bool has_target_pos, bool has_target_mat, bool has_q_out,
+                IkSettings<NC>& C) {
+  auto bad = [&](const char* msg) { s->err = std::string(api) + ": " + msg; return (int)SO101_ERR_ARG; };
+  if (!cfg) return bad("NULL config");
+  if (!has_target_pos || !has_q_out) return bad("target_pos and q_out are required");
+  if (cfg->mode < 0 || cfg->mode > 2) return bad("mode must be 0, 1 or 2");
+  if (cfg->max_iters < 0 || cfg->max_iters > 1000) return bad("max_iters must be 0 .. 1000");
+  if (!(cfg->tol_pos > 0.f) || !(cfg->tol_rot > 0.f) || !(cfg->rot_weight > 0.f) || !(cfg->max_step > 0.f)) return bad("tol_pos, tol_rot, rot_weight and max_step must be positive");
+  if (!(cfg->damping >= 0.f)) return bad("damping must not be negative");
+  for (int k = 0; k < nio; k++) if (!(cfg->q_lo[k] <= cfg->q_hi[k])) return bad("q_lo must not exceed q_hi");
+  if (nio < 32 && (free_mask >> nio) != 0u) return bad("free_mask has bits at or above the number of columns of the chain");
+  if (cfg->mode != 0 && !has_target_mat) return bad("modes 1 and 2 need target_mat");
+  C = IkSettings<NC>{};
+  C.mode = cfg->mode; C.max_iters = cfg->max_iters; C.tol_pos = cfg->tol_pos; C.tol_rot = cfg->tol_rot; C.rot_weight = cfg->rot_weight;
+  C.damping = cfg->damping; C.max_step = cfg->max_step; C.free_mask = free_mask;
+  for (int k = 0; k < nio; k++) { C.q_lo[k] = cfg->q_lo[k]; C.q_hi[k] = cfg->q_hi[k]; }
+  return SO101_OK;
 }

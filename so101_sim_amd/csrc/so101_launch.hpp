@@ -5,6 +5,9 @@
 #include <hip/hip_runtime.h>
 #include "so101_model.hpp"
 
+template <int NC> struct ToolChain;          // so101_tool_chain.hpp
+template <int NC> struct IkSettings;
+
 namespace so101 {
 
 struct StepIO {            // per-call arrays of so101_step (device pointers)
@@ -35,10 +38,13 @@ void launch_render(int n_render, hipStream_t st, const DevModel* m, const StepPa
                    int ncam, int height, int width, const float* planes, const int* plane_adr, float* frames, float* camframes,
                    float* depth, int* seg);
 
-// Cartesian tool control (so101_tool.hpp): lane = env, one wavefront per 64 entries.  q / q_init: [n][6] or NULL = the bound qpos of env env_index[i] (NULL: i)
-void launch_tool_pose(int n, hipStream_t st, const DevModel* m, const ToolArg& T, const float* q, const float* qpos, int n_envs, const int* env_index,
+// Cartesian tool control (so101_tool_chain.hpp): lane = entry, one wavefront per 64 entries; NC = 6 (SO100) and NC = 8 (the general-tree engine, both
+// builds) are instantiated.  q / q_init: [n][T.nio] or NULL = the bound qpos of env env_index[i] (NULL: i)
+template <int NC>
+void launch_tool_pose(int n, hipStream_t st, const ToolChain<NC>& T, const float* q, const float* qpos, int n_envs, const int* env_index,
                       float* pos, float* mat, float* jac);
-void launch_tool_ik(int n, hipStream_t st, const DevModel* m, const ToolArg& T, const IkArg& C, const float* target_pos, const float* target_mat,
+template <int NC>
+void launch_tool_ik(int n, hipStream_t st, const ToolChain<NC>& T, const IkSettings<NC>& C, const float* target_pos, const float* target_mat,
                     const float* q_init, const float* qpos, int n_envs, const int* env_index, float* q_out, float* residual, int* info);
 
 // pipelined step (Newton) -----------------------------------------------------------------------------------------

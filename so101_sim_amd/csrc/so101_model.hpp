@@ -293,7 +293,3 @@ struct ChainParams { const DevModel* m; StepParams P; DevBuffers B; EventBuffers
 #define RENDER_CAMFRAME 13       // floats per camera: pos[3], mat[9] (world from camera; columns x right, y up, z; the camera looks along -z), pixel scale
 struct RenderCam { int body; float pos[3], mat[9], scale; };      // body: -1 world, else as geom_dyn numbers the bodies (SO100: 0 .. NDYN - 1, tree: the body id); scale = 2 tan(fovy / 2) / H
 struct RenderCams { RenderCam cam[RENDER_MAXCAM]; };
-
-// ---- Cartesian tool control (so101_tool.hpp): the tool frame and the solver settings of one so101_tool_pose / so101_tool_ik call (kernel arguments)
-struct ToolArg { int body; float pos[3], mat[9]; };               // body: arm link 0 .. NARM - 1; mat row-major, the frame in that link's frame
-struct IkArg { int mode, max_iters; float tol_pos, tol_rot, rot_weight, damping, max_step, q_lo[NARM], q_hi[NARM]; };

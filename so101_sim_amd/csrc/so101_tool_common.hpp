@@ -1,5 +1,4 @@
-// Chain-independent pieces of Cartesian tool control, shared by the SO100 kernels (so101_tool.hpp) and the general-tree ones
-// (so101_tree_tool.hpp): the limit clamp, the rotation vector, the orientation error of the three modes and the damped least-squares step,
+// Chain-independent pieces of Cartesian tool control (the kernels: so101_tool_chain.hpp): the limit clamp, the rotation vector, the orientation error of the three modes and the damped least-squares step,
 // templated on the number of joint columns.  The algorithm they belong to is written down in include/so101.h (so101_tool_ik).
 #pragma once
 #include "so101_math.hpp"

@@ -1,7 +1,8 @@
-// Translation unit: physics-only stepping, the parity-test stage dump, reward, episode bookkeeping (Newton), the cameras, Cartesian tool control.
+// Translation unit: physics-only stepping, the parity-test stage dump, reward, episode bookkeeping (Newton), the cameras, Cartesian tool control
+// of both engines (the chain kernels for 6 columns - SO100 - and 8 - the general-tree engine, both builds).
 #include "so101_kernels.hpp"
 #include "so101_camera.hpp"
-#include "so101_tool.hpp"
+#include "so101_tool_chain.hpp"
 #include "so101_launch.hpp"
 
 __global__ void __launch_bounds__(64) k_begin(const DevModel* m, StepParams P, DevBuffers B, unsigned char* need_reset) {
@@ -56,13 +57,21 @@ void launch_render(int n_render, hipStream_t st, const DevModel* m, const StepPa
   hipLaunchKernelGGL(k_render_frames, dim3(n_render), dim3(64), 0, st, m, P, B, env_index, cams, ncam, frames, camframes);
   launch_render_image(n_render, st, m, frames, camframes, planes, plane_adr, ncam, height, width, depth, seg);
 }
-void launch_tool_pose(int n, hipStream_t st, const DevModel* m, const ToolArg& T, const float* q, const float* qpos, int n_envs, const int* env_index,
+template <int NC>
+void launch_tool_pose(int n, hipStream_t st, const ToolChain<NC>& T, const float* q, const float* qpos, int n_envs, const int* env_index,
                       float* pos, float* mat, float* jac) {
-  hipLaunchKernelGGL(k_tool_pose, dim3((unsigned int)((n + WAVE - 1) / WAVE)), dim3(64), 0, st, m, T, q, qpos, n_envs, env_index, n, pos, mat, jac);
+  hipLaunchKernelGGL(k_tool_pose<NC>, dim3((unsigned int)((n + WAVE - 1) / WAVE)), dim3(64), 0, st, T, q, qpos, n_envs, env_index, n, pos, mat, jac);
 }
-void launch_tool_ik(int n, hipStream_t st, const DevModel* m, const ToolArg& T, const IkArg& C, const float* target_pos, const float* target_mat,
+template <int NC>
+void launch_tool_ik(int n, hipStream_t st, const ToolChain<NC>& T, const IkSettings<NC>& C, const float* target_pos, const float* target_mat,
                     const float* q_init, const float* qpos, int n_envs, const int* env_index, float* q_out, float* residual, int* info) {
-  hipLaunchKernelGGL(k_tool_ik, dim3((unsigned int)((n + WAVE - 1) / WAVE)), dim3(64), 0, st, m, T, C, target_pos, target_mat, q_init, qpos, n_envs, env_index, n,
+  hipLaunchKernelGGL(k_tool_ik<NC>, dim3((unsigned int)((n + WAVE - 1) / WAVE)), dim3(64), 0, st, T, C, target_pos, target_mat, q_init, qpos, n_envs, env_index, n,
                      q_out, residual, info);
 }
+template void launch_tool_pose<6>(int, hipStream_t, const ToolChain<6>&, const float*, const float*, int, const int*, float*, float*, float*);
+template void launch_tool_pose<8>(int, hipStream_t, const ToolChain<8>&, const float*, const float*, int, const int*, float*, float*, float*);
+template void launch_tool_ik<6>(int, hipStream_t, const ToolChain<6>&, const IkSettings<6>&, const float*, const float*, const float*, const float*, int, const int*,
+                                float*, float*, int*);
+template void launch_tool_ik<8>(int, hipStream_t, const ToolChain<8>&, const IkSettings<8>&, const float*, const float*, const float*, const float*, int, const int*,
+                                float*, float*, int*);
 }  // namespace so101

@@ -4,7 +4,6 @@
 #include "so101_host.hpp"
 #include "so101_launch.hpp"
 #include "so101_tree.hpp"
-#include "so101_tree_tool.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -725,11 +724,13 @@ static void launch_tree_prepare(TreeHandle* s, hipStream_t stream) {
   if (hipGetLastError() == hipSuccess && hipEventRecord(s->prep_done, s->prep_stream) == hipSuccess) s->prep_pending = true;
 }
 
-// ---- Cartesian tool control (so101_tree_tool.hpp): the chain of a tool's body, computed per call on the host
+// ---- Cartesian tool control (so101_tool_chain.hpp, compiled in tu_misc.hip): the chain of a tool's body, computed per call on the host
 // The bodies from the world down to `body` that carry a hinge or slide joint become the columns, root first; the jointless bodies between them are
 // folded in double precision into the fixed transform in front of the next joint, what lies below the last joint into the tool's frame (pos, mat
 // row-major: identity when `tool` is NULL).  Returns SO101_OK or SO101_ERR_ARG with s->err set; `api` names the caller in the message.
-static int tree_tool_chain(TreeHandle* s, const char* api, int body, const so101_tree_tool* tool, TreeToolArg& T, int* dof /* [8] or NULL */) {
+constexpr int TREE_TOOL_MAXCOL = 8;
+static_assert(TJ_HINGE == TOOL_HINGE && TJ_SLIDE == TOOL_SLIDE, "the chain's column types are the joint types");
+static int tree_tool_chain(TreeHandle* s, const char* api, int body, const so101_tree_tool* tool, ToolChain<TREE_TOOL_MAXCOL>& T, int* dof /* [8] or NULL */) {
   const std::string a(api);
   const TreeModel& M = s->hm;
   if (body < 1 || body >= M.nbody) { s->err = a + ": tool body must be 1 .. nbody - 1 (a body id of the model)"; return SO101_ERR_ARG; }
@@ -753,7 +754,8 @@ static int tree_tool_chain(TreeHandle* s, const char* api, int body, const so101
     for (int i = 0; i < 4; i++) o[i] = r[i];
   };
   auto norm = [](double* q) { const double n = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]); for (int i = 0; i < 4; i++) q[i] /= n; };
-  T = TreeToolArg{};
+  T = ToolChain<TREE_TOOL_MAXCOL>{};
+  T.rquat[0] = 1.f;                           // (the root is the world)
   double P[3] = {0, 0, 0}, Q[4] = {1, 0, 0, 0};
   int k = 0;
   for (int i = np - 1; i >= 0; i--) {
@@ -775,7 +777,7 @@ static int tree_tool_chain(TreeHandle* s, const char* api, int body, const so101
       P[0] = P[1] = P[2] = 0.0; Q[0] = 1.0; Q[1] = Q[2] = Q[3] = 0.0;
     }
   }
-  T.ncol = ncol;
+  T.ncol = T.nio = ncol;
   double tp[3] = {0, 0, 0}, tm[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, w[3];
   if (tool) { for (int j = 0; j < 3; j++) tp[j] = tool->pos[j]; for (int j = 0; j < 9; j++) tm[j] = tool->mat[j]; }
   rot(Q, tp, w);
@@ -784,27 +786,6 @@ static int tree_tool_chain(TreeHandle* s, const char* api, int body, const so101
     const double col[3] = {tm[c], tm[3 + c], tm[6 + c]};
     rot(Q, col, w);
     for (int r = 0; r < 3; r++) T.tmat[3 * r + c] = (float)w[r];
-  }
-  return SO101_OK;
-}
-
-// the checks so101_tree_tool_pose and so101_tree_tool_ik share (those of the SO100 calls): the tool, the count and where the joints come from
-static int tree_tool_arguments(TreeHandle* s, const char* api, const so101_tree_tool* tool, bool has_q, const int32_t* env_index, int n, TreeToolArg& T) {
-  const std::string a(api);
-  if (!tool) { s->err = a + ": NULL tool"; return SO101_ERR_ARG; }
-  for (int i = 0; i < 3; i++) if (!std::isfinite(tool->pos[i])) { s->err = a + ": tool pos is not finite"; return SO101_ERR_ARG; }
-  for (int i = 0; i < 3; i++)
-    for (int j = 0; j < 3; j++) {
-      double d = 0.0;
-      for (int k = 0; k < 3; k++) d += (double)tool->mat[3 * k + i] * (double)tool->mat[3 * k + j];
-      if (!(std::fabs(d - (i == j ? 1.0 : 0.0)) <= 1e-4)) { s->err = a + ": tool mat is not orthonormal (|M^T M - I| > 1e-4)"; return SO101_ERR_ARG; }
-    }
-  if (int rc = tree_tool_chain(s, api, tool->body, tool, T, nullptr)) return rc;
-  if (n < 1 || n > (1 << 26)) { s->err = a + ": n must be 1 .. 2^26"; return SO101_ERR_ARG; }      // (the kernels index entries with int)
-  if (has_q && env_index) { s->err = a + ": env_index selects envs of the bound state, it cannot be combined with explicit joint values"; return SO101_ERR_ARG; }
-  if (!has_q) {
-    if (!s->bound) { s->err = a + ": state buffers not bound (call so101_tree_bind_state, or pass the joint values)"; return SO101_ERR_STATE; }
-    if (!env_index && n > s->n_envs) { s->err = a + ": n exceeds the envs of the handle"; return SO101_ERR_ARG; }
   }
   return SO101_OK;
 }
@@ -1098,10 +1079,10 @@ int TAPI(render)(TreeHandle* s, const so101_camera* cams, int ncam, int height, 
   return hip_ok(s, hipGetLastError(), "k_render") ? SO101_OK : SO101_ERR_HIP;
 }
 
-// ---- Cartesian tool control (so101_tree_tool.hpp)
+// ---- Cartesian tool control (so101_tool_chain.hpp)
 int TAPI(tool_chain)(TreeHandle* s, int body, int32_t* dof, int32_t* qposadr, int32_t* jnt_type) {
   if (!s) return SO101_ERR_ARG;
-  TreeToolArg T{};
+  ToolChain<TREE_TOOL_MAXCOL> T;
   int d[TREE_TOOL_MAXCOL] = {};
   if (int rc = tree_tool_chain(s, "so101_tree_tool_chain", body, nullptr, T, d)) return rc;
   for (int k = 0; k < T.ncol; k++) {
@@ -1114,10 +1095,9 @@ int TAPI(tool_chain)(TreeHandle* s, int body, int32_t* dof, int32_t* qposadr, in
 
 int TAPI(ik_default_config)(TreeHandle* s, int body, so101_tree_ik_config* cfg) {
   if (!s || !cfg) return SO101_ERR_ARG;
-  TreeToolArg T{};
+  ToolChain<TREE_TOOL_MAXCOL> T;
   if (int rc = tree_tool_chain(s, "so101_tree_ik_default_config", body, nullptr, T, nullptr)) return rc;
-  memset(cfg, 0, sizeof *cfg);
-  cfg->mode = 1; cfg->max_iters = 60; cfg->tol_pos = 1e-4f; cfg->tol_rot = 1e-3f; cfg->rot_weight = 0.1f; cfg->damping = 1e-6f; cfg->max_step = 0.5f;
+  ik_default_settings(cfg);
   int k = T.ncol;
   for (int b = body; b != 0; b = s->hm.body_parent[b]) {          // the chain's joints, tool side first
     const int j = s->hm.body_jnt[b];
@@ -1132,38 +1112,28 @@ int TAPI(ik_default_config)(TreeHandle* s, int body, so101_tree_ik_config* cfg) 
 
 int TAPI(tool_pose)(TreeHandle* s, const so101_tree_tool* tool, const float* q, const int32_t* env_index, int n, float* pos, float* mat, float* jac, void* stream) {
   if (!s) return SO101_ERR_ARG;
-  TreeToolArg T{};
-  if (int rc = tree_tool_arguments(s, "so101_tree_tool_pose", tool, q != nullptr, env_index, n, T)) return rc;
+  ToolChain<TREE_TOOL_MAXCOL> T;
+  if (int rc = check_tool_frame(s, "so101_tree_tool_pose", tool)) return rc;
+  if (int rc = tree_tool_chain(s, "so101_tree_tool_pose", tool->body, tool, T, nullptr)) return rc;
+  if (int rc = check_tool_entries(s, "so101_tree_tool_pose", q != nullptr, env_index != nullptr, n, s->bound, s->n_envs)) return rc;
   if (!pos && !mat && !jac) { s->err = "so101_tree_tool_pose: no output (pos, mat and jac are all NULL)"; return SO101_ERR_ARG; }
   GUARD_DEVICE(s);
-  hipLaunchKernelGGL(k_tree_tool_pose, dim3((unsigned int)((n + WAVE - 1) / WAVE)), dim3(64), 0, (hipStream_t)stream, T, q, (const float*)s->buf.qpos, s->n_envs,
-                     (const int*)env_index, n, pos, mat, jac);
-  return hip_ok(s, hipGetLastError(), "k_tree_tool_pose") ? SO101_OK : SO101_ERR_HIP;
+  so101::launch_tool_pose(n, (hipStream_t)stream, T, q, (const float*)s->buf.qpos, s->n_envs, (const int*)env_index, pos, mat, jac);
+  return hip_ok(s, hipGetLastError(), "k_tool_pose") ? SO101_OK : SO101_ERR_HIP;
 }
 
 int TAPI(tool_ik)(TreeHandle* s, const so101_tree_tool* tool, const so101_tree_ik_config* cfg, const float* target_pos, const float* target_mat, const float* q_init,
                   const int32_t* env_index, int n, float* q_out, float* residual, int32_t* info, void* stream) {
   if (!s) return SO101_ERR_ARG;
-  TreeToolArg T{};
-  if (int rc = tree_tool_arguments(s, "so101_tree_tool_ik", tool, q_init != nullptr, env_index, n, T)) return rc;
-  auto bad = [&](const char* msg) { s->err = std::string("so101_tree_tool_ik: ") + msg; return (int)SO101_ERR_ARG; };
-  if (!cfg) return bad("NULL config");
-  if (!target_pos || !q_out) return bad("target_pos and q_out are required");
-  if (cfg->mode < 0 || cfg->mode > 2) return bad("mode must be 0, 1 or 2");
-  if (cfg->max_iters < 0 || cfg->max_iters > 1000) return bad("max_iters must be 0 .. 1000");
-  if (!(cfg->tol_pos > 0.f) || !(cfg->tol_rot > 0.f) || !(cfg->rot_weight > 0.f) || !(cfg->max_step > 0.f)) return bad("tol_pos, tol_rot, rot_weight and max_step must be positive");
-  if (!(cfg->damping >= 0.f)) return bad("damping must not be negative");
-  for (int k = 0; k < T.ncol; k++) if (!(cfg->q_lo[k] <= cfg->q_hi[k])) return bad("q_lo must not exceed q_hi");
-  if (T.ncol < 32 && (cfg->free_mask >> T.ncol) != 0u) return bad("free_mask has bits at or above the number of columns of the chain");
-  if (cfg->mode != 0 && !target_mat) return bad("modes 1 and 2 need target_mat");
-  TreeIkArg C{};
-  C.mode = cfg->mode; C.max_iters = cfg->max_iters; C.tol_pos = cfg->tol_pos; C.tol_rot = cfg->tol_rot; C.rot_weight = cfg->rot_weight;
-  C.damping = cfg->damping; C.max_step = cfg->max_step; C.free_mask = cfg->free_mask;
-  for (int k = 0; k < T.ncol; k++) { C.q_lo[k] = cfg->q_lo[k]; C.q_hi[k] = cfg->q_hi[k]; }
+  ToolChain<TREE_TOOL_MAXCOL> T;
+  IkSettings<TREE_TOOL_MAXCOL> C;
+  if (int rc = check_tool_frame(s, "so101_tree_tool_ik", tool)) return rc;
+  if (int rc = tree_tool_chain(s, "so101_tree_tool_ik", tool->body, tool, T, nullptr)) return rc;
+  if (int rc = check_tool_entries(s, "so101_tree_tool_ik", q_init != nullptr, env_index != nullptr, n, s->bound, s->n_envs)) return rc;
+  if (int rc = ik_settings(s, "so101_tree_tool_ik", cfg, T.ncol, cfg ? cfg->free_mask : 0u, target_pos != nullptr, target_mat != nullptr, q_out != nullptr, C)) return rc;
   GUARD_DEVICE(s);
-  hipLaunchKernelGGL(k_tree_tool_ik, dim3((unsigned int)((n + WAVE - 1) / WAVE)), dim3(64), 0, (hipStream_t)stream, T, C, target_pos, target_mat, q_init,
-                     (const float*)s->buf.qpos, s->n_envs, (const int*)env_index, n, q_out, residual, (int*)info);
-  return hip_ok(s, hipGetLastError(), "k_tree_tool_ik") ? SO101_OK : SO101_ERR_HIP;
+  so101::launch_tool_ik(n, (hipStream_t)stream, T, C, target_pos, target_mat, q_init, (const float*)s->buf.qpos, s->n_envs, (const int*)env_index, q_out, residual, (int*)info);
+  return hip_ok(s, hipGetLastError(), "k_tool_ik") ? SO101_OK : SO101_ERR_HIP;
 }
 
 int TAPI(get_diag)(TreeHandle* s, int* out /* [n_envs][8] device or host-visible memory */, void* stream) {

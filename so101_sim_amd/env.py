@@ -24,6 +24,7 @@ from . import native
 from ._dmenv import BoundedArray, Array, StepType, TimeStep
 from .calibration import SO101Calibration
 from .model import scenes
+from .tool_control import ToolControl
 
 DEFAULT_CONTROL_TIMESTEP = 0.02
 PHYSICS_TIMESTEP = 0.002
@@ -98,7 +99,7 @@ class _PhysicsView:
         raise NotImplementedError("rendering is outside the MI355X hot path (SURVEY.md 8b)")
 
 
-class BatchedEnvironment:
+class BatchedEnvironment(ToolControl):
     def __init__(self, task: SO100HandOverTask, n_envs: int = 1, time_limit: float = float("inf"),
                  random_state=None, device=None, env_id_base: int = 0, solver_iterations: int = 0,
                  solver_tolerance: float = -1.0, settle_max_substeps: int = 1000, solver: str = "newton",
@@ -361,12 +362,7 @@ class BatchedEnvironment:
         torch = self.torch
         cams = _cameras.resolve(camera)
         self._ensure_hull_planes()
-        idx, n = None, self.n_envs
-        if env_ids is not None:
-            idx = torch.as_tensor(env_ids, dtype=torch.int32, device=self.device).reshape(-1).contiguous()
-            n = int(idx.numel())
-            if n == 0 or int(idx.min()) < 0 or int(idx.max()) >= self.n_envs:
-                raise ValueError("env_ids must name at least one env of this batch")
+        idx, n = self._env_index(env_ids)
         depth = torch.empty(n, len(cams), int(height), int(width), dtype=torch.float32, device=self.device)
         seg = torch.empty(n, len(cams), int(height), int(width), dtype=torch.int32, device=self.device) if segmentation else None
         self.sim.render([c.spec() for c in cams], height, width, idx.data_ptr() if idx is not None else None, n,
@@ -381,50 +377,17 @@ class BatchedEnvironment:
             self._tools = _tools.so100_tools(self.meta, blobfmt.unpack(scenes.load_blob(self.task.object_name, "f32")[0]))
         return _tools.resolve(tool, self._tools)
 
-    def _env_index(self, env_ids):
-        """env_ids (sequence, tensor or None) -> (int32 device tensor or None, count)"""
-        if env_ids is None:
-            return None, self.n_envs
-        torch = self.torch
-        idx = torch.as_tensor(env_ids, dtype=torch.int32, device=self.device).reshape(-1).contiguous()
-        n = int(idx.numel())
-        if n == 0 or int(idx.min()) < 0 or int(idx.max()) >= self.n_envs:
-            raise ValueError("env_ids must name at least one env of this batch")
-        return idx, n
+    def _tool_columns(self, t):
+        return 6
 
-    def _f32(self, a):
-        """array-like or tensor -> float32 tensor on the env's device (numpy input is copied: it may be read-only)"""
-        if isinstance(a, np.ndarray):
-            a = np.array(a, dtype=np.float32)
-        return self.torch.as_tensor(a, dtype=self.torch.float32, device=self.device)
-
-    def _joint_rows(self, q, what):
-        q = self._f32(q)
-        if q.dim() == 1:
-            q = q.unsqueeze(0)
-        if q.dim() != 2 or q.shape[1] != 6 or q.shape[0] < 1:
-            raise ValueError(f"{what} must be [n, 6] joint angles, got {tuple(q.shape)}")
-        return q.contiguous()
+    def _ik_config(self, t, mode, config):
+        return self.sim.ik_config(mode=mode, **config)
 
     def tool_pose(self, tool="fixed_jaw_pad", env_ids=None, q=None, jacobian: bool = False):
         """World pose of a tool frame (tools.Tool or a name of the scene's tools) on the GPU (so101_tool_pose): at the current qpos of
         the envs `env_ids` (None = all), or at explicit joint angles `q` [n, 6].  Returns (pos [n, 3], mat [n, 3, 3]) and, with
         jacobian=True, jac [n, 6, 6] - rows 0-2 the translational, rows 3-5 the rotational Jacobian of MuJoCo's mj_jacSite."""
-        torch = self.torch
-        t = self._resolve_tool(tool)
-        if q is not None:
-            if env_ids is not None:
-                raise ValueError("env_ids selects envs of the current state: it cannot be combined with q")
-            q = self._joint_rows(q, "q")
-            idx, n = None, int(q.shape[0])
-        else:
-            idx, n = self._env_index(env_ids)
-        pos = torch.empty(n, 3, dtype=torch.float32, device=self.device)
-        mat = torch.empty(n, 3, 3, dtype=torch.float32, device=self.device)
-        jac = torch.empty(n, 6, 6, dtype=torch.float32, device=self.device) if jacobian else None
-        self.sim.tool_pose(t.spec(), q.data_ptr() if q is not None else None, idx.data_ptr() if idx is not None else None, n,
-                           pos.data_ptr(), mat.data_ptr(), jac.data_ptr() if jac is not None else None, self._stream())
-        return (pos, mat, jac) if jacobian else (pos, mat)
+        return self._tool_pose(tool, env_ids, q, jacobian)
 
     def solve_ik(self, target_pos, target_mat=None, tool="fixed_jaw_pad", mode=None, q_init=None, env_ids=None, **config):
         """Joint angles that bring a tool to Cartesian targets, one damped least-squares solve per row on the GPU (so101_tool_ik).
@@ -435,41 +398,7 @@ class BatchedEnvironment:
         (max_iters, tol_pos, tol_rot, rot_weight, damping, max_step, q_lo, q_hi; include/so101.h so101_ik_config).
         Returns (q [n, 6], converged [n] bool, residual [n, 2] = position error in metres and orientation error in radians at q,
         iters [n] int32, -1 where not converged).  Joints beyond the tool's link keep their starting value."""
-        torch = self.torch
-        t = self._resolve_tool(tool)
-        tp = self._f32(target_pos)
-        if tp.dim() == 1:
-            tp = tp.unsqueeze(0)
-        if tp.dim() != 2 or tp.shape[1] != 3 or tp.shape[0] < 1:
-            raise ValueError(f"target_pos must be [n, 3], got {tuple(tp.shape)}")
-        tp = tp.contiguous()
-        n = int(tp.shape[0])
-        tm = None
-        if target_mat is not None:
-            tm = self._f32(target_mat).reshape(-1, 3, 3).contiguous()
-            if tm.shape[0] != n:
-                raise ValueError(f"target_mat must be [{n}, 3, 3], got {tuple(tm.shape)}")
-        if mode is None:
-            mode = 0 if tm is None else 1
-        if q_init is not None:
-            if env_ids is not None:
-                raise ValueError("env_ids selects envs of the current state: it cannot be combined with q_init")
-            q_init = self._joint_rows(q_init, "q_init")
-            if q_init.shape[0] != n:
-                raise ValueError(f"q_init must be [{n}, 6], got {tuple(q_init.shape)}")
-            idx = None
-        else:
-            idx, k = self._env_index(env_ids)
-            if idx is not None and k != n:
-                raise ValueError(f"env_ids names {k} envs for {n} targets")
-        cfg = self.sim.ik_config(mode=int(mode), **config)
-        q = torch.empty(n, 6, dtype=torch.float32, device=self.device)
-        residual = torch.empty(n, 2, dtype=torch.float32, device=self.device)
-        iters = torch.empty(n, dtype=torch.int32, device=self.device)
-        self.sim.tool_ik(t.spec(), cfg, tp.data_ptr(), tm.data_ptr() if tm is not None else None,
-                         q_init.data_ptr() if q_init is not None else None, idx.data_ptr() if idx is not None else None, n,
-                         q.data_ptr(), residual.data_ptr(), iters.data_ptr(), self._stream())
-        return q, iters >= 0, residual, iters
+        return self._solve_ik(target_pos, target_mat, tool, mode, q_init, env_ids, config)
 
     def cartesian_action(self, target_pos, target_mat=None, jaw=None, tool="fixed_jaw_pad", mode=None, **config):
         """An [N, 6] action for step_tensor() that commands the tool of every env to a Cartesian target: the IK solution started

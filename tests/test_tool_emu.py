@@ -97,6 +97,16 @@ def test_reference_ik_converges_on_every_shared_case(seed):
         print(f"fp64 IK, seed {seed}, mode {mode}: 512/512 converged, worst {worst} iterations")
 
 
+def test_reference_ik_converges_on_every_inner_link_case():
+    """a condition on the inputs of the inner-link device tests: all 65 cases, position only, within the default 60 iterations in fp64"""
+    ref, tool, cs = tc.reference(), tc.spec(tc.INNER_TOOL), tc.inner_cases()
+    assert tool[0] == 2 and cs["pos"].shape == (65, 3) and cs["q_init"].shape == (65, 6)
+    assert np.all(cs["q_init"] >= ref.lo) and np.all(cs["q_init"] <= ref.hi)
+    infos = [ref.ik(tool, cs["pos"][i], None, cs["q_init"][i], mode=0)[1] for i in range(tc.N_INNER)]
+    print(f"fp64 IK, inner-link cases: iterations {infos}")
+    assert min(infos) >= 0 and max(infos) <= 60, infos
+
+
 def _tool_struct(tool):
     return native.tool_spec(tool.spec())
 
@@ -205,3 +215,7 @@ def test_emulated_ik_reaches_the_first_cases(blobs, mode):
         rp, rr_ = ref.residual(q[i], tc.spec(tool), cs["pos"][i], cs["mat"][i], mode)
         assert rp <= 1e-4 + 2e-6 and rr_ <= 1e-3 + 1e-5, (i, rp, rr_)
         assert abs(res[i, 0] - rp) <= 2e-6 and abs(res[i, 1] - rr_) <= 1e-5
+
+
+def test_emulated_ik_of_a_tool_on_an_inner_link(blobs):
+    tc.check_inner_link(ArraySim(blobs["f32"], 1, backend="emu"), 8)

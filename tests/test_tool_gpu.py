@@ -103,6 +103,11 @@ def test_ik_reaches_the_target_in_fp64(blobs, mode):
     assert np.array_equal(bits(qb[keep]), bits(qe[keep])) and np.array_equal(ib[keep], ie[keep])
 
 
+def test_ik_of_a_tool_on_an_inner_link(blobs):
+    """a tool on link 2: three walked columns, three joints beyond it (tests/tool_cases.py check_inner_link)"""
+    tc.check_inner_link(ArraySim(blobs["f32"], 1, backend=BACKEND), tc.N_INNER)
+
+
 @pytest.mark.parametrize("mode", [1, 2])
 def test_every_env_is_solved_independently(blobs, mode):
     """one wavefront of cases that start at their target, cases of seed 2 and one unreachable target: each entry's bits are those of solving it

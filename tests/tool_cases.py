@@ -18,6 +18,9 @@ N_CASES = 512
 IDENTITY_TOOL = tools.Tool("link0", 0)
 # a tool on the moving jaw (link 5), off its origin and rotated: every column of the Jacobian is in use
 JAW_TOOL = tools.Tool.from_xyaxes("moving_jaw_tip", 5, (0.004, -0.03, 0.012), (0.6, 0.8, 0.0, -0.32, 0.24, 0.92))
+# a tool on an inner link (link 2): three walked columns, and three trailing joints that the IK clamps and hands back
+INNER_TOOL = tools.Tool.from_xyaxes("lower_arm_point", 2, (0.02, -0.09, 0.015), (0.0, 0.6, 0.8, 1.0, 0.0, 0.0))
+N_INNER, INNER_SEED = 65, 3
 
 
 @functools.lru_cache(maxsize=None)
@@ -57,6 +60,45 @@ def ik_cases(seed: int):
     """the cases of the scene's own tool (fixed_jaw_pad): dict of read-only arrays q_target [512, 6], q_init [512, 6], pos [512, 3], mat [512, 3, 3],
     computed once per seed"""
     return _cases(int(seed))
+
+
+@functools.lru_cache(maxsize=None)
+def inner_cases(seed: int = INNER_SEED):
+    """65 position-only cases of INNER_TOOL: dict of read-only arrays pos [65, 3] = FK of joints drawn over their whole range (the first three
+    move the tool) and q_init [65, 6] within the range: the three joints beyond the tool's link over all of it, the three walked ones within
+    1 rad of the target's.  Position-only damped least squares with clamping stalls at a joint limit on the wrong branch of the arm for 31 % of
+    starts drawn over the whole range (200 draws, whatever the tool's offset), 1 % at 1 rad: from there about every second seed gives 65
+    solvable cases.  test_tool_emu.py asserts that the fp64 reference converges on all of them within the default 60 iterations."""
+    ref = reference()
+    u = np.random.RandomState(seed).uniform(size=(2, N_INNER, 6))
+    q_target, q_init = ref.lo + u[0] * (ref.hi - ref.lo), ref.lo + u[1] * (ref.hi - ref.lo)
+    q_init[:, :3] = np.clip(q_target[:, :3] + 1.0 * (2.0 * u[1, :, :3] - 1.0), ref.lo[:3], ref.hi[:3])
+    pos = np.array([ref.fk(q, spec(INNER_TOOL), jacobian=False)[0] for q in q_target])
+    out = dict(q_init=q_init, pos=pos)
+    for a in out.values():
+        a.setflags(write=False)
+    return out
+
+
+def check_inner_link(sim, n):
+    """so101_tool_ik (mode 0) and so101_tool_pose for the first n inner-link cases on an ArraySim of either backend: every solve converges, the
+    reported residual is the fp64 one of q_out within the margins of tests/test_tool_gpu.py (2e-6 m, 1e-5 rad), the joints beyond the tool's
+    link come back as clip(q_init) bit for bit, and their Jacobian columns are +0."""
+    ref, cs = reference(), inner_cases()
+    bits = lambda a: np.ascontiguousarray(a).view(np.int32)
+    q, res, info = tool_ik(sim, INNER_TOOL, cs["pos"][:n], None, cs["q_init"][:n], mode=0)
+    print(f"inner-link IK, n = {n}: iterations {info.tolist()}")
+    assert np.all(info >= 0), np.flatnonzero(info < 0)
+    worst = np.zeros(2)
+    for i in range(n):
+        rp, rr_ = ref.residual(q[i], spec(INNER_TOOL), cs["pos"][i], None, 0)
+        worst = np.maximum(worst, [abs(res[i, 0] - rp), abs(res[i, 1] - rr_)])
+    print(f"inner-link IK, n = {n}: reported - fp64 residual worst {worst[0]:.3e} m {worst[1]:.3e} rad")
+    assert worst[0] <= 2e-6 and worst[1] <= 1e-5
+    held = np.clip(cs["q_init"][:n, 3:].astype(np.float32), ref.lo[3:].astype(np.float32), ref.hi[3:].astype(np.float32))
+    assert np.array_equal(bits(q[:, 3:]), bits(held))
+    _, _, jac = tool_pose(sim, INNER_TOOL, n, q=q)
+    assert np.all(bits(jac[:, :, 3:]) == 0) and np.any(jac[:, :, :3] != 0)
 
 
 def random_q(seed: int, n: int):

@@ -36,6 +36,61 @@ def zaxis_rotvec(z, zt):
     return rotvec_from(np.cross(z, zt), float(z @ zt), fb / np.linalg.norm(fb))
 
 
+def errors(fk, q, target_pos, target_mat, mode):
+    """fk: q -> (p, M, J).  -> (e_p, e_r, M, J) of the three modes"""
+    p, M, J = fk(q)
+    ep = np.asarray(target_pos, dtype=np.float64) - p
+    if mode == 0:
+        er = np.zeros(3)
+    elif mode == 1:
+        er = zaxis_rotvec(M[:, 2], np.asarray(target_mat, dtype=np.float64).reshape(3, 3)[:, 2])
+    else:
+        er = rotvec(np.asarray(target_mat, dtype=np.float64).reshape(3, 3) @ M.T)
+    return ep, er, M, J
+
+
+def residual(fk, q, target_pos, target_mat, mode):
+    ep, er, _, _ = errors(fk, q, target_pos, target_mat, mode)
+    return float(np.linalg.norm(ep)), float(np.linalg.norm(er))
+
+
+def dls_ik(fk, lo, hi, free, target_pos, target_mat, q_init, **cfg):
+    """-> (q, info, (|e_p|, |e_r|)): the algorithm of include/so101.h in fp64 over the columns of fk's Jacobian; free [ncol] bool: the columns
+    solved for, the others are zero in Jw and keep clip(q_init)"""
+    c = dict(DEFAULTS, **cfg)
+    ncol = len(lo)
+    mode, w = c["mode"], c["rot_weight"]
+    q = np.clip(np.asarray(q_init, dtype=np.float64), lo, hi)
+    finite = np.all(np.isfinite(target_pos)) and (mode == 0 or np.all(np.isfinite(target_mat)))
+    it = 0
+    while True:
+        ep, er, M, J = errors(fk, q, target_pos, target_mat, mode)
+        res = (float(np.linalg.norm(ep)), float(np.linalg.norm(er)))
+        if not finite:
+            return q, -1, res
+        if res[0] <= c["tol_pos"] and res[1] <= c["tol_rot"]:
+            return q, it, res
+        if it == c["max_iters"]:
+            return q, -1, res
+        Jr = J[3:]
+        if mode == 0:
+            Jr = np.zeros((3, ncol))
+        elif mode == 1:
+            z = M[:, 2]
+            Jr = (np.eye(3) - np.outer(z, z)) @ Jr
+        Jw = np.vstack([J[:3], w * Jr])
+        Jw[:, ~free] = 0.0
+        e = np.r_[ep, w * er]
+        A = Jw @ Jw.T + (e @ e + c["damping"]) * np.eye(6)
+        L = np.linalg.cholesky(A)
+        dq = Jw.T @ np.linalg.solve(L.T, np.linalg.solve(L, e))
+        big = np.abs(dq).max()
+        if big > c["max_step"]:
+            dq = dq * (c["max_step"] / big)
+        q = np.where(free, np.clip(q + dq, lo, hi), q)
+        it += 1
+
+
 class ToolRef:
     def __init__(self, blob_f64: bytes):
         m = blobfmt.unpack(blob_f64)
@@ -82,51 +137,13 @@ class ToolRef:
         return p, M, J
 
     def errors(self, q, tool, target_pos, target_mat, mode):
-        p, M, J = self.fk(q, tool)
-        ep = np.asarray(target_pos, dtype=np.float64) - p
-        if mode == 0:
-            er = np.zeros(3)
-        elif mode == 1:
-            er = zaxis_rotvec(M[:, 2], np.asarray(target_mat, dtype=np.float64).reshape(3, 3)[:, 2])
-        else:
-            er = rotvec(np.asarray(target_mat, dtype=np.float64).reshape(3, 3) @ M.T)
-        return ep, er, M, J
+        return errors(lambda x: self.fk(x, tool), q, target_pos, target_mat, mode)
 
     def residual(self, q, tool, target_pos, target_mat, mode):
-        ep, er, _, _ = self.errors(q, tool, target_pos, target_mat, mode)
-        return float(np.linalg.norm(ep)), float(np.linalg.norm(er))
+        return residual(lambda x: self.fk(x, tool), q, target_pos, target_mat, mode)
 
     def ik(self, tool, target_pos, target_mat, q_init, lo=None, hi=None, **cfg):
-        """-> (q, info, (|e_p|, |e_r|)): the algorithm of include/so101.h in fp64"""
-        c = dict(DEFAULTS, **cfg)
+        """-> (q, info, (|e_p|, |e_r|)): dls_ik over the six arm joints, all of them free"""
         lo = self.lo if lo is None else np.asarray(lo, dtype=np.float64)
         hi = self.hi if hi is None else np.asarray(hi, dtype=np.float64)
-        mode, w = c["mode"], c["rot_weight"]
-        q = np.clip(np.asarray(q_init, dtype=np.float64), lo, hi)
-        finite = np.all(np.isfinite(target_pos)) and (mode == 0 or np.all(np.isfinite(target_mat)))
-        it = 0
-        while True:
-            ep, er, M, J = self.errors(q, tool, target_pos, target_mat, mode)
-            res = (float(np.linalg.norm(ep)), float(np.linalg.norm(er)))
-            if not finite:
-                return q, -1, res
-            if res[0] <= c["tol_pos"] and res[1] <= c["tol_rot"]:
-                return q, it, res
-            if it == c["max_iters"]:
-                return q, -1, res
-            Jr = J[3:]
-            if mode == 0:
-                Jr = np.zeros((3, 6))
-            elif mode == 1:
-                z = M[:, 2]
-                Jr = (np.eye(3) - np.outer(z, z)) @ Jr
-            Jw = np.vstack([J[:3], w * Jr])
-            e = np.r_[ep, w * er]
-            A = Jw @ Jw.T + (e @ e + c["damping"]) * np.eye(6)
-            L = np.linalg.cholesky(A)
-            dq = Jw.T @ np.linalg.solve(L.T, np.linalg.solve(L, e))
-            big = np.abs(dq).max()
-            if big > c["max_step"]:
-                dq = dq * (c["max_step"] / big)
-            q = np.clip(q + dq, lo, hi)
-            it += 1
+        return dls_ik(lambda x: self.fk(x, tool), lo, hi, np.ones(6, dtype=bool), target_pos, target_mat, q_init, **cfg)

@@ -6,7 +6,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from tests.tool_ref import DEFAULTS, rotvec, zaxis_rotvec
+from tests.tool_ref import dls_ik, errors, residual
 from tests.tree_raycast_ref import TJ_FREE, TJ_HINGE, TJ_SLIDE, TreeRaycastRef
 
 
@@ -77,57 +77,17 @@ class TreeToolRef(TreeRaycastRef):
         return self.fk_qpos(self.full_qpos(tool[0], q), tool, jacobian)
 
     def errors(self, q, tool, target_pos, target_mat, mode):
-        p, M, J = self.fk(q, tool)
-        ep = np.asarray(target_pos, dtype=np.float64) - p
-        if mode == 0:
-            er = np.zeros(3)
-        elif mode == 1:
-            er = zaxis_rotvec(M[:, 2], np.asarray(target_mat, dtype=np.float64).reshape(3, 3)[:, 2])
-        else:
-            er = rotvec(np.asarray(target_mat, dtype=np.float64).reshape(3, 3) @ M.T)
-        return ep, er, M, J
+        return errors(lambda x: self.fk(x, tool), q, target_pos, target_mat, mode)
 
     def residual(self, q, tool, target_pos, target_mat, mode):
-        ep, er, _, _ = self.errors(q, tool, target_pos, target_mat, mode)
-        return float(np.linalg.norm(ep)), float(np.linalg.norm(er))
+        return residual(lambda x: self.fk(x, tool), q, target_pos, target_mat, mode)
 
     def ik(self, tool, target_pos, target_mat, q_init, lo=None, hi=None, free_mask=None, **cfg):
-        """-> (q, info, (|e_p|, |e_r|)): the algorithm of include/so101.h in fp64; free_mask None = the hinge columns"""
-        c = dict(DEFAULTS, **cfg)
+        """-> (q, info, (|e_p|, |e_r|)): dls_ik over the chain's columns; free_mask None = the hinge columns"""
         body = tool[0]
         dlo, dhi = self.limits(body)
         lo = dlo if lo is None else np.asarray(lo, dtype=np.float64)
         hi = dhi if hi is None else np.asarray(hi, dtype=np.float64)
-        ncol = len(lo)
         free_mask = self.hinge_mask(body) if free_mask is None else int(free_mask)
-        free = np.array([(free_mask >> k) & 1 for k in range(ncol)], dtype=bool)
-        mode, w = c["mode"], c["rot_weight"]
-        q = np.clip(np.asarray(q_init, dtype=np.float64), lo, hi)
-        finite = np.all(np.isfinite(target_pos)) and (mode == 0 or np.all(np.isfinite(target_mat)))
-        it = 0
-        while True:
-            ep, er, M, J = self.errors(q, tool, target_pos, target_mat, mode)
-            res = (float(np.linalg.norm(ep)), float(np.linalg.norm(er)))
-            if not finite:
-                return q, -1, res
-            if res[0] <= c["tol_pos"] and res[1] <= c["tol_rot"]:
-                return q, it, res
-            if it == c["max_iters"]:
-                return q, -1, res
-            Jr = J[3:]
-            if mode == 0:
-                Jr = np.zeros((3, ncol))
-            elif mode == 1:
-                z = M[:, 2]
-                Jr = (np.eye(3) - np.outer(z, z)) @ Jr
-            Jw = np.vstack([J[:3], w * Jr])
-            Jw[:, ~free] = 0.0
-            e = np.r_[ep, w * er]
-            A = Jw @ Jw.T + (e @ e + c["damping"]) * np.eye(6)
-            L = np.linalg.cholesky(A)
-            dq = Jw.T @ np.linalg.solve(L.T, np.linalg.solve(L, e))
-            big = np.abs(dq).max()
-            if big > c["max_step"]:
-                dq = dq * (c["max_step"] / big)
-            q = np.where(free, np.clip(q + dq, lo, hi), q)
-            it += 1
+        free = np.array([(free_mask >> k) & 1 for k in range(len(lo))], dtype=bool)
+        return dls_ik(lambda x: self.fk(x, tool), lo, hi, free, target_pos, target_mat, q_init, **cfg)
