@@ -30,7 +30,7 @@ struct G16 {
   DEV static void argmax(float& val, int& idx) { float x = 0.f, y = 0.f, z = 0.f; row_argmax3(val, idx, x, y, z); }
   // the payload-free row reduction (wave.hpp row_argmax): same winner.  The list-backed subsets (HullSub) use it for the five patch reductions of
   // support_multi(); the staged-hull row pass of k_narrow<true> keeps argmax() and with it the code it was measured with.
-#ifdef SO101_EMU      // (the lane-thread emulation brings its own wave primitives and has the payload form only)
+#if defined(SO101_EMU) && !defined(SO101_EMU_ROW_ARGMAX)      // (a lane-thread emulation header that has the payload form only)
   DEV static void argmax_lean(float& val, int& idx) { argmax(val, idx); }
 #else
   DEV static void argmax_lean(float& val, int& idx) { row_argmax(val, idx); }

@@ -77,8 +77,9 @@ DEV void normquat(float* q) {
   q[0] *= inv; q[1] *= inv; q[2] *= inv; q[3] *= inv;
 }
 // sin and cos of one angle: Cody-Waite reduction by pi/2 (three constants, exact products through fma) and the
-// cephes minimax polynomials on [-pi/4, pi/4]; <= 2 ulp for |x| < 1e4 rad.  The libm sinf/cosf expand to ~220
-// instructions each (large-argument path), and the kinematics needs six pairs per substep.
+// cephes minimax polynomials on [-pi/4, pi/4]; <= 2 ulp for |x| < 1e4 rad (measured 1.52 / 1.55 on 10^6 inputs,
+// tests/blocks_cases.py check_sincos), sin(-0) = -0.  The libm sinf/cosf expand to ~220 instructions each
+// (large-argument path), and the kinematics needs six pairs per substep.
 DEV void sincos_f(float x, float* sn, float* cs) {
   float k = rintf(x * 0.63661977236758134308f);
   float r = fmaf(-k, 1.57079625129699707031f, x);
@@ -87,6 +88,7 @@ DEV void sincos_f(float x, float* sn, float* cs) {
   float z = r * r;
   float s = fmaf(r * z, fmaf(z, fmaf(z, -1.9515295891e-4f, 8.3321608736e-3f), -1.6666654611e-1f), r);
   float c = fmaf(z * z, fmaf(z, fmaf(z, 2.443315711809948e-5f, -1.388731625493765e-3f), 4.166664568298827e-2f), fmaf(-0.5f, z, 1.f));
+  s = x == 0.f ? x : s;            // sin(-0) = -0: the reduction and the polynomial both end in (+0) + (-0) = +0
   int q = (int)k;
   float s1 = (q & 1) ? c : s, c1 = (q & 1) ? s : c;
   *sn = (q & 2) ? -s1 : s1;

@@ -1026,9 +1026,10 @@ DEV float contact_block(const TCon& C, const float* D, int dim, const float* r, 
       float hk = -Dm * mu * mu * U[k] * mk / T;
       Hc[k] = hk; Hc[k * 6] = hk;
 #pragma unroll
-      for (int l = 1; l < 6; l++) if (l < dim) {
+      for (int l = 1; l < 6; l++) if (l <= k) {        // (the lower triangle, mirrored: the products below are not symmetric in k, l bit for bit)
         float ml = fr[l];
-        Hc[k * 6 + l] = Dm * mu * mu * mk * ml * U[k] * U[l] / (T * T) - Dm * sN * mu * mk * ml * ((k == l ? 1.f : 0.f) / T - U[k] * U[l] / (T * T * T));
+        float h = Dm * mu * mu * mk * ml * U[k] * U[l] / (T * T) - Dm * sN * mu * mk * ml * ((k == l ? 1.f : 0.f) / T - U[k] * U[l] / (T * T * T));
+        Hc[k * 6 + l] = h; Hc[l * 6 + k] = h;
       }
     }
   }

@@ -156,7 +156,10 @@ __device__ __forceinline__ void wave_argmax(float& val, int& idx) {
 }
 
 // argmax that also carries a 3-vector payload held by each lane (the winning lane's payload is broadcast
-// with v_readlane, no memory access): used by the hull support function
+// with v_readlane, no memory access): used by the hull support function.  The source is the lowest lane whose candidate
+// (its index where it holds the maximum, 0x7fffffff elsewhere) equals the smallest one.  0x7fffffff is the index of a lane
+// without an entry: when it is the winning index, every lane qualifies and lane 0's payload comes out, whether or not lane 0
+// holds the maximum - callers give real entries smaller indices.
 __device__ __forceinline__ void wave_argmax3(float& val, int& idx, float& x, float& y, float& z) {
   float mx = wave_max_f(val);
   int cand = (val == mx) ? idx : 0x7fffffff;

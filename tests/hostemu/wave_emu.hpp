@@ -100,6 +100,20 @@ inline void row_argmax3(float& val, int& idx, float& x, float& y, float& z) {
   pthread_barrier_wait(&emu_row_barrier[row]);
   val = ov; idx = oi; x = ox; y = oy; z = oz;
 }
+// the same reduction without a payload (wave.hpp row_argmax)
+#define SO101_EMU_ROW_ARGMAX 1
+inline void row_argmax(float& val, int& idx) {
+  float* pv = emu_blk->pv;
+  int* pi = emu_blk->pi;
+  int t = threadIdx.x, row = t >> 4, r0 = t & ~15, src = r0;
+  pv[t] = val; pi[t] = idx;
+  pthread_barrier_wait(&emu_row_barrier[row]);
+  for (int i = r0 + 1; i < r0 + 16; i++)
+    if (pv[i] > pv[src] || (pv[i] == pv[src] && pi[i] < pi[src])) src = i;
+  float ov = pv[src]; int oi = pi[src];
+  pthread_barrier_wait(&emu_row_barrier[row]);
+  val = ov; idx = oi;
+}
 // matrix cores (wave.hpp): D += A (32 x 2) * B (2 x 32) in the lane layout of v_mfma_f32_32x32x2_f32
 struct mfma_acc16 { float v[16]; float& operator[](int i) { return v[i]; } const float& operator[](int i) const { return v[i]; } };
 inline mfma_acc16 mfma_32x32x2(float a, float b, mfma_acc16 acc) {
