@@ -4,12 +4,10 @@
 #include "so101_host.hpp"
 #include "so101_launch.hpp"
 
-#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <map>
 #include <memory>
 #include <string>
 #include <vector>
@@ -50,10 +48,8 @@ struct so101_sim : HostHandle {      // (so101_host.hpp: device, owned allocatio
   int* diag = nullptr;
   // reset prefetch: cache of settled initial states, filled by k_prepare on a low-priority side stream
   PrepBuffers prep{};
-  hipStream_t prep_stream = nullptr;
+  SideStream side;                         // (so101_host.hpp)
   int prep_scan = 0;                       // next slice of the second look-ahead (launch_prepare)
-  hipEvent_t prep_done = nullptr, main_ev = nullptr;
-  bool prep_pending = false;
   int prep_waves = 0;
   float* conres_full = nullptr;            // [N][MAXCAND][CONRES_DIM] contact records of pipelines 2 and 3 (allocated on first use)
   unsigned long long* mq_slot = nullptr;   // merged launches (pipeline = 3): chunk rings, queue words and launch counters of the chains
@@ -65,9 +61,7 @@ struct so101_sim : HostHandle {      // (so101_host.hpp: device, owned allocatio
   bool chain_params_valid = false;
   PipeBuffers pipe{};          // scratch of the pipelined step (group 0's view; the groups differ in work/counters)
   static constexpr int MAXGROUPS = 8;
-  hipStream_t group_stream[MAXGROUPS] = {};
-  hipEvent_t group_done[MAXGROUPS] = {};
-  hipEvent_t step_begin = nullptr;
+  StreamLanes<MAXGROUPS> groups;           // one stream per launch chain (so101_host.hpp)
   EventBuffers ev{};           // per-env flag accumulator + global event counters (so101_get_events)
   // captured launch sequence of the pipelined step (see so101_step)
   hipGraphExec_t graph_exec = nullptr;
@@ -233,20 +227,13 @@ int build_model(so101_sim* s, const BlobView& b) {
   return SO101_OK;
 }
 
-// Launches k_prepare behind whatever `stream` holds now, unless the previous one is still running (it picks up
-// every env whose next episode is missing, so skipping a launch only delays the refill).
+// k_prepare on the side stream, behind whatever `stream` holds now (SideStream, so101_host.hpp).
 // (pool resets are plain copies: nothing to prefetch)
-bool prefetch_on(const so101_sim* s) { return s->cfg.prefetch_resets && s->prep_stream && s->cfg.solver == SO101_SOLVER_NEWTON && s->prep.pool_size == 0; }
+bool prefetch_on(const so101_sim* s) { return s->cfg.prefetch_resets && s->side.stream && s->cfg.solver == SO101_SOLVER_NEWTON && s->prep.pool_size == 0; }
 
 void launch_prepare(so101_sim* s, hipStream_t stream, bool wide = false) {
-  if (!prefetch_on(s)) return;
-  if (s->prep_pending) {
-    if (hipEventQuery(s->prep_done) != hipSuccess) { (void)hipGetLastError(); return; }
-    s->prep_pending = false;
-  }
-  if (hipEventRecord(s->main_ev, stream) != hipSuccess) return;
-  if (hipStreamWaitEvent(s->prep_stream, s->main_ev, 0) != hipSuccess) return;
-  if (hipMemsetAsync(s->prep.cursor, 0, 2 * sizeof(int), s->prep_stream) != hipSuccess) return;
+  if (!prefetch_on(s) || !s->side.begin(stream)) return;
+  if (hipMemsetAsync(s->prep.cursor, 0, 2 * sizeof(int), s->side.stream) != hipSuccess) return;
   // `wide` (after an explicit so101_reset, when nothing is stepping yet): the first fill of the cache - two episodes for every
   // env - at the width of the machine (0.8 s for 4096 envs) instead of 256 wavefronts beside the first ~600 control steps, during
   // which every env whose physics diverged had to settle inside the step call (130 ms for the whole batch each time)
@@ -259,15 +246,11 @@ void launch_prepare(so101_sim* s, hipStream_t stream, bool wide = false) {
   static const int prep_slice = getenv("SO101_PREP_SLICE") ? atoi(getenv("SO101_PREP_SLICE")) : 0;
   if (!wide && prep_slice > 0 && s->n_envs > prep_slice) { C.scan_first = s->prep_scan; C.scan_count = prep_slice; s->prep_scan = (s->prep_scan + prep_slice) % s->n_envs; }
   else { C.scan_first = 0; C.scan_count = 0; }
-  so101::launch_prepare(waves, s->prep_stream, s->dm, make_params(s), s->buf, C);
-  if (hipEventRecord(s->prep_done, s->prep_stream) == hipSuccess) s->prep_pending = true;
+  so101::launch_prepare(waves, s->side.stream, s->dm, make_params(s), s->buf, C);
+  s->side.launched();
 }
 
-bool drain_prepare(so101_sim* s) {
-  if (!s->prep_stream) return true;
-  s->prep_pending = false;
-  return hip_ok(s, hipStreamSynchronize(s->prep_stream), "hipStreamSynchronize(prepare)");
-}
+bool drain_prepare(so101_sim* s) { return s->side.drain(s, "hipStreamSynchronize(prepare)"); }
 
 // the cache the kernels see: none when the prefetch is off (PGS, or prefetch_resets = 0)
 PrepBuffers prep_view(const so101_sim* s) {
@@ -323,12 +306,7 @@ int so101_create(const void* blob, size_t bytes, int n_envs, int device, uint64_
     PrepBuffers& C = s->prep;
     bool ok = scratch_alloc(s, &C.qpos, 2 * NQ * n, 0, "hipMalloc(prep)") && scratch_alloc(s, &C.qvel, 2 * NV * n, 0, "hipMalloc(prep)") &&
               scratch_alloc(s, &C.warm, 2 * NV * n, 0, "hipMalloc(prep)") && scratch_alloc(s, &C.tag, 2 * n, 0xFF, "hipMalloc(prep)") &&
-              scratch_alloc(s, &C.cursor, (size_t)2, 0, "hipMalloc(prep)") && scratch_alloc(s, &C.flags, 2 * n, 0, "hipMalloc(prep)");
-    int lo = 0, hi = 0;
-    ok = ok && hip_ok(s, hipDeviceGetStreamPriorityRange(&lo, &hi), "hipDeviceGetStreamPriorityRange") &&
-         hip_ok(s, hipStreamCreateWithPriority(&s->prep_stream, hipStreamNonBlocking, lo), "hipStreamCreateWithPriority") &&
-         hip_ok(s, hipEventCreateWithFlags(&s->prep_done, hipEventDisableTiming), "hipEventCreate") &&
-         hip_ok(s, hipEventCreateWithFlags(&s->main_ev, hipEventDisableTiming), "hipEventCreate");
+              scratch_alloc(s, &C.cursor, (size_t)2, 0, "hipMalloc(prep)") && scratch_alloc(s, &C.flags, 2 * n, 0, "hipMalloc(prep)") && s->side.setup(s);
     // one wave per CU at most: the refill runs beside the stepping kernels, it must not crowd them out
     if (ok) s->prep_waves = n_envs < 256 ? n_envs : 256; else rc = SO101_ERR_HIP;
   }
@@ -357,18 +335,13 @@ int so101_create(const void* blob, size_t bytes, int n_envs, int device, uint64_
     // for: ensure_experimental_buffers())
     // (kernel experiments: SO101_GROUP_PRIO=1 gives the chain of the most expensive envs - slice 0 of the cost-sorted order - the highest
     //  stream priority and the cheapest slice the lowest)
-    int plo = 0, phi = 0;
-    hipDeviceGetStreamPriorityRange(&plo, &phi);
+    int plo = 0, phi = 0, prio[so101_sim::MAXGROUPS];
+    (void)hipDeviceGetStreamPriorityRange(&plo, &phi);
     const bool gprio_on = getenv("SO101_GROUP_PRIO") && atoi(getenv("SO101_GROUP_PRIO")) != 0;
-    for (int g = 0; g < so101_sim::MAXGROUPS && ok; g++) {
-      int pr = !gprio_on ? 0 : (g == 0 ? phi : (g >= 3 ? plo : (plo + phi) / 2));
-      // (measured in round 5 and removed again: the chains pinned to disjoint sets of 64 CUs by hipExtStreamCreateWithCUMask - kernels of different
-      //  chains then never share a CU or its instruction cache - ran at 459 k against 666 k env-steps/s without graph replay; 48 and 32 CUs 283 / 281 k)
-      ok = hip_ok(s, gprio_on ? hipStreamCreateWithPriority(&s->group_stream[g], hipStreamNonBlocking, pr) : hipStreamCreateWithFlags(&s->group_stream[g], hipStreamNonBlocking), "hipStreamCreate") &&
-           hip_ok(s, hipEventCreateWithFlags(&s->group_done[g], hipEventDisableTiming), "hipEventCreate");
-    }
-    ok = ok && hip_ok(s, hipEventCreateWithFlags(&s->step_begin, hipEventDisableTiming), "hipEventCreate");
-    if (!ok) rc = SO101_ERR_HIP;
+    for (int g = 0; g < so101_sim::MAXGROUPS; g++) prio[g] = g == 0 ? phi : (g >= 3 ? plo : (plo + phi) / 2);
+    // (measured in round 5 and removed again: the chains pinned to disjoint sets of 64 CUs by hipExtStreamCreateWithCUMask - kernels of different
+    //  chains then never share a CU or its instruction cache - ran at 459 k against 666 k env-steps/s without graph replay; 48 and 32 CUs 283 / 281 k)
+    if (!(ok && s->groups.setup(s, gprio_on ? prio : nullptr))) rc = SO101_ERR_HIP;
   }
   if (rc != SO101_OK) { g_create_error = s->err; so101_destroy(s); return rc; }
   *out = s;
@@ -380,14 +353,6 @@ void so101_destroy(so101_sim* s) {
   {
     DeviceGuard guard(s);
     drop_graph(s);
-    if (s->prep_stream) { (void)hipStreamSynchronize(s->prep_stream); (void)hipStreamDestroy(s->prep_stream); }
-    for (int g = 0; g < so101_sim::MAXGROUPS; g++) {
-      if (s->group_stream[g]) { (void)hipStreamSynchronize(s->group_stream[g]); (void)hipStreamDestroy(s->group_stream[g]); }
-      if (s->group_done[g]) (void)hipEventDestroy(s->group_done[g]);
-    }
-    if (s->step_begin) (void)hipEventDestroy(s->step_begin);
-    if (s->prep_done) (void)hipEventDestroy(s->prep_done);
-    if (s->main_ev) (void)hipEventDestroy(s->main_ev);
     free_owned(s);
   }
   delete s;
@@ -541,11 +506,10 @@ static int enqueue_pipelined(so101_sim* s, hipStream_t st, const so101::StepIO& 
   for (int g = 0; g < G && equal_slices; g++) equal_slices = bounds[g + 1] - bounds[g] == n / G;
   so101::launch_order(st, s->pipe.cost, s->pipe.order, s->chain_cls, n, equal_slices && n % G == 0 ? G : 1);
   LAUNCH_CHECK(s, "k_order");
-  if (G > 1 && !hip_ok(s, hipEventRecord(s->step_begin, st), "hipEventRecord")) return SO101_ERR_HIP;
+  if (!s->groups.fork(s, st, G)) return SO101_ERR_HIP;
   for (int g = 0; g < G; g++) {
     int e0 = bounds[g], ng = bounds[g + 1] - bounds[g];
     if (ng <= 0) continue;
-    hipStream_t gs = G == 1 ? st : s->group_stream[g];
     PipeBuffers W = s->pipe;
     W.counters = s->pipe.counters + 4 * MAXSUB * g;      // [MAXSUB][2] work items / cursor, then [MAXSUB][2] heavy / light items (so101_pipeline.hpp)
     // the slice's pool of contact records: CONRES_PER_ENV per env plus a floor of MAXCAND, so that ONE env can always place every
@@ -593,7 +557,8 @@ static int enqueue_pipelined(so101_sim* s, hipStream_t st, const so101::StepIO& 
     // (a handful of envs - the reference's own N = 1: a step is a chain of dependent single-env launches, so the pairs of an env are spread
     //  over 16 wavefronts instead of queued on one or two)
     nw = nw < 16 ? 16 : (nw < 4096 ? nw : 4096);
-    if (G > 1 && !hip_ok(s, hipStreamWaitEvent(gs, s->step_begin, 0), "hipStreamWaitEvent")) return SO101_ERR_HIP;
+    hipStream_t gs;
+    if (!s->groups.stream_of(s, g, &gs)) return SO101_ERR_HIP;
     if (!hip_ok(s, hipMemsetAsync(W.counters, 0, sizeof(int) * 4 * MAXSUB, gs), "hipMemsetAsync(pipe)")) return SO101_ERR_HIP;
     if (s->cfg.pipeline == 3) {
       // merged launches: the narrowphase of substep k + 1 rides in the solve launch of substep k (so101_chain.hpp)
@@ -615,8 +580,7 @@ static int enqueue_pipelined(so101_sim* s, hipStream_t st, const so101::StepIO& 
       }
     }
     LAUNCH_CHECK(s, "k_pipe_solve");
-    if (G > 1 && !(hip_ok(s, hipEventRecord(s->group_done[g], gs), "hipEventRecord") &&
-                   hip_ok(s, hipStreamWaitEvent(st, s->group_done[g], 0), "hipStreamWaitEvent"))) return SO101_ERR_HIP;
+    if (!s->groups.join(s, g)) return SO101_ERR_HIP;
   }
   return SO101_OK;
 }
@@ -795,16 +759,10 @@ int so101_reward(so101_sim* s, float* reward, void* stream) {
 int so101_set_hull_planes(so101_sim* s, const float* planes, const int32_t* plane_adr) {
   if (!s) return SO101_ERR_ARG;
   if (!planes || !plane_adr) { s->err = "so101_set_hull_planes: NULL argument"; return SO101_ERR_ARG; }
-  const int ng = s->hm.ngeom;
   if (!check_hull_planes(s, "so101_set_hull_planes", s->render, planes, plane_adr)) return SO101_ERR_ARG;          // (so101_host.hpp)
   GUARD_DEVICE(s);
-  // (a render in flight reads the old tables: they stay allocated until so101_destroy)
-  const size_t n = (size_t)plane_adr[ng];
-  float* dp = nullptr; int* da = nullptr;
-  if (!scratch_alloc(s, &dp, 4 * n, -1, "hipMalloc(hull planes)") || !scratch_alloc(s, &da, (size_t)ng + 1, -1, "hipMalloc(hull planes)")) return SO101_ERR_HIP;
-  if (n && !hip_ok(s, hipMemcpy(dp, planes, sizeof(float) * 4 * n, hipMemcpyHostToDevice), "hipMemcpy(hull planes)")) return SO101_ERR_HIP;
-  if (!hip_ok(s, hipMemcpy(da, plane_adr, sizeof(int) * ((size_t)ng + 1), hipMemcpyHostToDevice), "hipMemcpy(hull planes)")) return SO101_ERR_HIP;
-  s->render.hull_planes = dp; s->render.plane_adr = da; s->render.planes_set = true;
+  if (!s->render.upload_planes(s, planes, plane_adr)) return SO101_ERR_HIP;
+  s->scratch_bytes += s->render.plane_bytes((size_t)plane_adr[s->hm.ngeom]);
   return SO101_OK;
 }
 
@@ -816,18 +774,10 @@ int so101_render(so101_sim* s, const so101_camera* cams, int ncam, int height, i
   RenderHost& R = s->render;
   if (R.has_meshes() && !R.planes_set) { s->err = "so101_render: the scene has mesh geoms and no hull planes (call so101_set_hull_planes)"; return SO101_ERR_STATE; }
   GUARD_DEVICE(s);
-  if ((size_t)n_render > R.cap) {
-    // grown outside any stream order: hipFree waits for the device, so a render still reading the old scratch finishes first
-    for (void* p : {(void*)R.frames, (void*)R.cams}) {
-      auto it = std::find(s->owned.begin(), s->owned.end(), p);
-      if (p && it != s->owned.end()) { s->owned.erase(it); (void)hipFree(p); }
-    }
-    s->scratch_bytes -= sizeof(float) * R.cap * ((size_t)s->hm.ngeom * RENDER_FRAME + RENDER_MAXCAM * RENDER_CAMFRAME);
-    R.frames = nullptr; R.cams = nullptr; R.cap = 0;
-    if (!scratch_alloc(s, &R.frames, (size_t)n_render * s->hm.ngeom * RENDER_FRAME, -1, "hipMalloc(render)") ||
-        !scratch_alloc(s, &R.cams, (size_t)n_render * RENDER_MAXCAM * RENDER_CAMFRAME, -1, "hipMalloc(render)")) return SO101_ERR_HIP;
-    R.cap = (size_t)n_render;
-  }
+  const size_t cap = R.cap;
+  const bool grown = R.reserve(s, (size_t)n_render);
+  s->scratch_bytes += R.frame_bytes() * R.cap - R.frame_bytes() * cap;          // (the scratch it had is gone when the growth failed)
+  if (!grown) return SO101_ERR_HIP;
   so101::launch_render(n_render, (hipStream_t)stream, s->dm, make_params(s), s->buf, (const int*)env_index, rc, ncam, height, width,
                        R.hull_planes, R.plane_adr, R.frames, R.cams, depth, (int*)seg);
   LAUNCH_CHECK(s, "k_render");

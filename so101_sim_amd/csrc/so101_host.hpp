@@ -1,5 +1,5 @@
-// Host layer shared by the two engines' handles (so101_sim of so101_hip.hip, TreeHandle of tu_tree.hip): device guard, HIP error
-// helper, owned device allocations, and the loader that puts a model blob's collision geometry into a DevModel.  Host code only.
+// Host layer shared by the two engines' handles (so101_sim of so101_hip.hip, TreeHandle of so101_tree_host.hpp): device guard, HIP error helper, owned
+// allocations, streams and events, the prefetch's side stream, the env slices' streams, the loader of a blob's collision geometry, cameras, tool calls.
 // The general-tree engine is compiled twice (tu_tree.hip inside tv32 / tv64) and the emulator build of the tests includes every .hip
 // into one translation unit: everything here is inline, outside those namespaces, and depends on no T* macro.
 #pragma once
@@ -16,10 +16,12 @@
 #include <string>
 #include <vector>
 
-// what every handle carries: its device, the device allocations it owns, its last error message
+// what every handle carries: its device, the device allocations, streams and events it owns, its last error message
 struct HostHandle {
   int device = 0;
   std::vector<void*> owned;
+  std::vector<hipStream_t> streams;
+  std::vector<hipEvent_t> events;
   std::string err;
 };
 
@@ -68,10 +70,74 @@ bool upload_one(HostHandle* s, const T& v, T** out) {
   return dev_alloc(s, out, 1, -1, "hipMalloc(model)") && hip_ok(s, hipMemcpy(*out, &v, sizeof(T), hipMemcpyHostToDevice), "hipMemcpy(model)");
 }
 
-inline void free_owned(HostHandle* s) {
-  for (void* p : s->owned) (void)hipFree(p);
-  s->owned.clear();
+// a non-blocking stream owned by the handle (prioritised: created at `priority` of hipDeviceGetStreamPriorityRange); an event without timing
+inline bool new_stream(HostHandle* s, hipStream_t* out, bool prioritised = false, int priority = 0) {
+  bool ok = prioritised ? hip_ok(s, hipStreamCreateWithPriority(out, hipStreamNonBlocking, priority), "hipStreamCreateWithPriority")
+                        : hip_ok(s, hipStreamCreateWithFlags(out, hipStreamNonBlocking), "hipStreamCreate");
+  if (ok) s->streams.push_back(*out);
+  return ok;
 }
+inline bool new_event(HostHandle* s, hipEvent_t* out) {
+  if (!hip_ok(s, hipEventCreateWithFlags(out, hipEventDisableTiming), "hipEventCreate")) return false;
+  s->events.push_back(*out);
+  return true;
+}
+
+// everything the handle owns: the streams drained first, so nothing of them still runs on memory that is about to go
+inline void free_owned(HostHandle* s) {
+  for (hipStream_t st : s->streams) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
+  for (hipEvent_t ev : s->events) (void)hipEventDestroy(ev);
+  for (void* p : s->owned) (void)hipFree(p);
+  s->streams.clear(); s->events.clear(); s->owned.clear();
+}
+
+// The side stream of a reset prefetch: one launch at a time on the lowest-priority stream, behind whatever the caller's stream held when it was enqueued:
+// `if (side.begin(st)) { <launches on side.stream>; side.launched(); }`.  begin() is false while the previous launch still runs (the next one refills).
+struct SideStream {
+  hipStream_t stream = nullptr;
+  hipEvent_t done = nullptr, main_ev = nullptr;
+  bool pending = false;
+  bool setup(HostHandle* s) {
+    int lo = 0, hi = 0;
+    return hip_ok(s, hipDeviceGetStreamPriorityRange(&lo, &hi), "hipDeviceGetStreamPriorityRange") && new_stream(s, &stream, true, lo) &&
+           new_event(s, &done) && new_event(s, &main_ev);
+  }
+  bool begin(hipStream_t caller) {
+    if (pending && hipEventQuery(done) != hipSuccess) { (void)hipGetLastError(); return false; }      // (not ready is a status, not an error to keep)
+    pending = false;
+    return hipEventRecord(main_ev, caller) == hipSuccess && hipStreamWaitEvent(stream, main_ev, 0) == hipSuccess;
+  }
+  void launched() { if (hipEventRecord(done, stream) == hipSuccess) pending = true; }
+  bool drain(HostHandle* s, const char* what) {
+    pending = false;
+    return !stream || hip_ok(s, hipStreamSynchronize(stream), what);
+  }
+};
+
+// Env slices whose launch chains overlap, each on a stream of its own: fork(caller, n) once, then per lane g its chain on stream_of(g) and
+// join(g).  One lane runs on the caller's stream and touches no event.
+template <int MAX>
+struct StreamLanes {
+  hipStream_t stream[MAX] = {}, caller = nullptr;
+  hipEvent_t done[MAX] = {}, begin = nullptr;
+  int n = 1;
+  bool setup(HostHandle* s, const int* priority = nullptr) {      // priority: [MAX] stream priorities, NULL for plain streams
+    for (int g = 0; g < MAX; g++)
+      if (!new_stream(s, &stream[g], priority != nullptr, priority ? priority[g] : 0) || !new_event(s, &done[g])) return false;
+    return new_event(s, &begin);
+  }
+  bool fork(HostHandle* s, hipStream_t from, int lanes) {
+    caller = from; n = lanes;
+    return n == 1 || hip_ok(s, hipEventRecord(begin, caller), "hipEventRecord");
+  }
+  bool stream_of(HostHandle* s, int g, hipStream_t* out) {         // lane g's stream, behind what the caller's held at the fork
+    *out = n == 1 ? caller : stream[g];
+    return n == 1 || hip_ok(s, hipStreamWaitEvent(*out, begin, 0), "hipStreamWaitEvent");
+  }
+  bool join(HostHandle* s, int g) {
+    return n == 1 || (hip_ok(s, hipEventRecord(done[g], stream[g]), "hipEventRecord") && hip_ok(s, hipStreamWaitEvent(caller, done[g], 0), "hipStreamWaitEvent"));
+  }
+};
 
 inline void h_quat2mat(float* m, const float* q) {
   float w = q[0], x = q[1], y = q[2], z = q[3];
@@ -165,8 +231,38 @@ struct RenderHost {
   bool planes_set = false;
   float *frames = nullptr, *cams = nullptr;      // device [cap][ngeom][RENDER_FRAME], [cap][RENDER_MAXCAM][RENDER_CAMFRAME]
   size_t cap = 0;
-  void load(const BlobView& b) { gtype = b.I("geom_type"); vertadr = b.I("geom_vertadr"); vertnum = b.I("geom_vertnum"); vert = b.F("mesh_vert"); }
+  int ngeom = 0;
+  void load(const BlobView& b) { ngeom = b.I("ngeom")[0]; gtype = b.I("geom_type"); vertadr = b.I("geom_vertadr"); vertnum = b.I("geom_vertnum"); vert = b.F("mesh_vert"); }
   bool has_meshes() const { for (int t : gtype) if (t == G_MESH) return true; return false; }
+  // device bytes of the planes of an upload / of the frames scratch per rendered env (SO101_INFO_SCRATCH_BYTES counts them)
+  size_t plane_bytes(size_t n) const { return sizeof(float) * 4 * (n ? n : 1) + sizeof(int) * ((size_t)ngeom + 1); }
+  size_t frame_bytes() const { return sizeof(float) * ((size_t)ngeom * RENDER_FRAME + RENDER_MAXCAM * RENDER_CAMFRAME); }
+
+  // planes that passed check_hull_planes() become the tables of the next render (a render in flight reads the old ones: they stay allocated
+  // until the handle goes); false: a HIP call failed (s->err)
+  bool upload_planes(HostHandle* s, const float* planes, const int32_t* adr) {
+    const size_t n = (size_t)adr[ngeom];
+    float* dp = nullptr; int* da = nullptr;
+    if (!dev_alloc(s, &dp, 4 * n, -1, "hipMalloc(hull planes)") || !dev_alloc(s, &da, (size_t)ngeom + 1, -1, "hipMalloc(hull planes)")) return false;
+    if (n && !hip_ok(s, hipMemcpy(dp, planes, sizeof(float) * 4 * n, hipMemcpyHostToDevice), "hipMemcpy(hull planes)")) return false;
+    if (!hip_ok(s, hipMemcpy(da, adr, sizeof(int) * ((size_t)ngeom + 1), hipMemcpyHostToDevice), "hipMemcpy(hull planes)")) return false;
+    hull_planes = dp; plane_adr = da; planes_set = true;
+    return true;
+  }
+  // frames scratch for n_render envs.  Grown outside any stream order: hipFree waits for the device, so a render still reading the old scratch
+  // finishes first
+  bool reserve(HostHandle* s, size_t n_render) {
+    if (n_render <= cap) return true;
+    for (void* p : {(void*)frames, (void*)cams}) {
+      auto it = std::find(s->owned.begin(), s->owned.end(), p);
+      if (p && it != s->owned.end()) { s->owned.erase(it); (void)hipFree(p); }
+    }
+    frames = nullptr; cams = nullptr; cap = 0;
+    if (!dev_alloc(s, &frames, n_render * ngeom * RENDER_FRAME, -1, "hipMalloc(render)") ||
+        !dev_alloc(s, &cams, n_render * RENDER_MAXCAM * RENDER_CAMFRAME, -1, "hipMalloc(render)")) return false;
+    cap = n_render;
+    return true;
+  }
 };
 
 // The contract of so101_set_hull_planes (include/so101.h) on HOST arrays, before anything is uploaded: non-mesh geoms have empty ranges, a mesh

@@ -10,7 +10,7 @@
 // The chain is built on the host, once per call, and arrives by value in the kernel-argument segment (wave-uniform scalar loads), as do the
 // solver settings.  SO100: the base as the root, one hinge column per arm link up to the tool's (so101_hip.hip).  Tree: the bodies between the
 // world and the tool's body that carry a hinge or slide joint, the jointless ones folded in double precision into the next column
-// (tree_tool_chain in tu_tree.hip).  Loops over columns are unrolled to NC with `k < ncol` / `k < nio` as wave-uniform branches, so every
+// (tree_tool_chain in so101_tree_host.hpp).  Loops over columns are unrolled to NC with `k < ncol` / `k < nio` as wave-uniform branches, so every
 // per-lane array is indexed by constants and lives in registers: no LDS, no scratch (scripts/kernel_resources.py).
 //
 // Per column the expressions of kinematics() (so101_device.hpp) and tree::kinematics() (so101_tree.hpp): xp += R pos, xq = xq * quat, hinge:

@@ -721,7 +721,7 @@ DEV void collision(const TreeModel* tm, const DevModel* gm, TreeLDS& L, bool nar
   wave_sync();
 }
 
-// ------------------------------------------------------------------ the narrowphase in a launch of its own (round 4, tu_tree.hip: k_tree_pipe_*)
+// ------------------------------------------------------------------ the narrowphase in a launch of its own (round 4, so101_tree_kernels.hpp: k_tree_pipe_*)
 // A control step as a launch chain: per substep one launch with a wavefront per CANDIDATE PAIR of the whole batch (persistent wavefronts
 // pulling from a work list, as k_narrow of the SO100 step) and one with a wavefront per env for everything else.  Inside k_tree_step the env's
 // wavefront walks its 18 (ALOHA) to 59 (Dining) candidates one after the other at ~12 us each while the hull caches and the EPA polytope
@@ -1407,6 +1407,28 @@ DEV void euler(const TreeModel* tm, TreeLDS& L) {
   wave_sync();
 }
 
+// mj_checkPos / Vel / Acc: NaN or beyond 1e10 ends the episode (the caller sees flag 8 and resets the env); wave-uniform
+DEV bool diverged(const TreeModel* tm, const TreeLDS& L) {
+  int lane = wave_lane();
+  auto bounded = [](float x) { return fabsf(x) <= 1e10f; };
+  bool ok = true;
+  if (lane < tm->nq) ok = ok && bounded(L.qpos[lane]);
+  if (lane < tm->nv) ok = ok && bounded(L.qvel[lane]) && bounded(L.qacc[lane]);
+  return wave_ballot(!ok) != 0ull;
+}
+
+// Lane 0's records (the caller holds the lane condition).  store_diag: the env's record of so101_tree_get_diag ([8] ints; [5] is
+// tree_finish_step's, so101_tree_kernels.hpp).  save / load_pipe_diag: between the launches of a chain the flags and the diagnostics of an
+// env's last computed substep wait in the hand-off buffers (the flags are read back when a launch starts).
+DEV void store_diag(const TreeBuffers& B, const TreeLDS& L, int e) {
+  if (B.diag) { int* d = B.diag + 8 * e; d[0] = L.ncon; d[1] = L.nrow; d[2] = L.iters; d[3] = L.ncand; d[4] = L.flags; }
+}
+DEV void save_pipe_diag(const TreePipe& P, const TreeLDS& L, int e) {
+  P.pflags[e] = L.flags; P.pdiag[4 * e] = L.nrow; P.pdiag[4 * e + 1] = L.iters; P.pdiag[4 * e + 2] = L.ncon; P.pdiag[4 * e + 3] = L.ncand;
+}
+DEV void load_pipe_diag(const TreePipe& P, TreeLDS& L, int e) {
+  L.nrow = P.pdiag[4 * e]; L.iters = P.pdiag[4 * e + 1]; L.ncon = P.pdiag[4 * e + 2]; L.ncand = P.pdiag[4 * e + 3];
+}
 
 // ================================================================== env layer of the ALOHA hand-over tasks
 // (so101_sim/tasks/base/aloha2_task.py:279-444 action / observables / reset, so101_sim/tasks/hand_over.py:36-56,246-349
@@ -1583,10 +1605,8 @@ DEV void env_settle(const TreeModel* tm, const DevModel* gm, const TreeTask& T, 
   for (int k = 0; k < T.settle_max && !settled; k++) {
     forward(tm, gm, L, G, T.iterations, T.tolerance);
     euler(tm, L);
-    bool ok = true;
-    if (lane < tm->nq) ok = ok && fabsf(L.qpos[lane]) <= 1e10f;
-    if (lane < tm->nv) ok = ok && fabsf(L.qvel[lane]) <= 1e10f && fabsf(L.qacc[lane]) <= 1e10f;
-    if (wave_ballot(!ok) != 0ull) { if (lane == 0) L.flags |= 8; break; }
+    bool bad = diverged(tm, L);       // (a named bool: with the call inside the condition the kernels' register allocation changes)
+    if (bad) { if (lane == 0) L.flags |= 8; break; }
     if (lane < tm->njnt) { L.qpos[lane] = q0; L.qvel[lane] = 0.f; }     // (one-dof joints come first in qpos / qvel; dm_control holds them)
     wave_sync();
     float mv = 0.f, ma = 0.f;

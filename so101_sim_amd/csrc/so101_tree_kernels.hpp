@@ -1,0 +1,448 @@
+// General-tree engine: the kernels over the device functions of so101_tree.hpp, launched by tu_tree.hip and so101_tree_host.hpp.  Included
+// once per build of the engine (TREE_VARIANT): no include guard, every macro is undefined before it is defined.
+// so101_tree_debug_forward layout (floats per env; dims[7..14] of so101_tree_dims report it): counts, bias, qacc_smooth, qacc [TV each],
+// body positions [TB][3], mass matrix [TV][TV], contacts [TCON][10] (pos3 normal3 dist geom1 geom2 dim), normal forces [TCON]
+#undef TDBG_COUNTS
+#undef TDBG_BIAS
+#undef TDBG_QSM
+#undef TDBG_QACC
+#undef TDBG_XPOS
+#undef TDBG_M
+#undef TDBG_CON
+#undef TDBG_FORCE
+#undef TDBG_DIM
+#define TDBG_COUNTS 0        // ncon, nrow, iters, ncand, flags, nscalar
+#define TDBG_BIAS 8
+#define TDBG_QSM (TDBG_BIAS + TV)
+#define TDBG_QACC (TDBG_QSM + TV)
+#define TDBG_XPOS (TDBG_QACC + TV)     // [TB][3]
+#define TDBG_M (TDBG_XPOS + 3 * TB)    // [TV][TV]
+#define TDBG_CON (TDBG_M + TV * TV)    // [TCON][10]
+#define TDBG_FORCE (TDBG_CON + 10 * TCON)
+#define TDBG_DIM (((TDBG_FORCE + TCON) + 63) / 64 * 64)
+
+namespace TREE_NS {
+using tree::TreePipe;
+
+__global__ void __launch_bounds__(64) k_tree_physics(const TreeModel* tm, const DevModel* gm, TreeBuffers B, int N, int nsub, int iterations, float tolerance) {
+  BLOCK_SHARED(TreeLDS, L);
+  int e = blockIdx.x, lane = wave_lane();
+  if (lane == 0) L.flags = 0;
+  tree::load_state(tm, L, B, e, N);
+  TreeScratch G = tree::scratch_of(B, e);
+  int bad = 0;
+  for (int s = 0; s < nsub; s++) {
+    tree::forward(tm, gm, L, G, iterations, tolerance);
+    tree::euler(tm, L);
+    if (tree::diverged(tm, L)) { bad = 1; break; }
+  }
+  if (lane == 0 && bad) L.flags |= 8;
+  tree::store_state(tm, L, B, e, N);
+  if (lane == 0) tree::store_diag(B, L, e);
+}
+
+__global__ void __launch_bounds__(64) k_tree_forward(const TreeModel* tm, const DevModel* gm, TreeBuffers B, int N, int iterations, float tolerance, float* out, int phases) {
+  BLOCK_SHARED(TreeLDS, L);
+  int e = blockIdx.x, lane = wave_lane();
+  if (lane == 0) L.flags = 0;
+#ifdef TREE_PROF
+  if (lane < 32) L.prof[lane] = 0u;
+#endif
+  tree::load_state(tm, L, B, e, N);
+  TreeScratch G = tree::scratch_of(B, e);
+  tree::forward(tm, gm, L, G, iterations, tolerance, phases);
+  float* o = out + (size_t)e * TDBG_DIM;
+  int nv = tm->nv, nb = tm->nbody;
+  if (lane == 0) { o[0] = (float)L.ncon; o[1] = (float)L.nrow; o[2] = (float)L.iters; o[3] = (float)L.ncand; o[4] = (float)L.flags; o[5] = (float)L.nscalar; }
+  if (lane < nv) {
+    o[TDBG_BIAS + lane] = L.bias[lane]; o[TDBG_QSM + lane] = L.qsm[lane]; o[TDBG_QACC + lane] = L.qacc[lane];
+    for (int r = 0; r < nv; r++) o[TDBG_M + r * TV + lane] = L.M[r][lane];
+  }
+  if (lane < nb) for (int k = 0; k < 3; k++) o[TDBG_XPOS + 3 * lane + k] = L.xpos[lane][k];
+#ifdef TREE_PROF
+  wave_sync();
+  if (lane < 16) o[TDBG_M + lane] = (float)L.prof[lane];         // (profiling variant: the phase clocks take the first slots of the mass-matrix dump)
+#endif
+  for (int ci = lane; ci < L.ncon; ci += WAVE) {
+    const TCon& c = L.con[ci];
+    float* q = o + TDBG_CON + 10 * ci;
+    for (int k = 0; k < 3; k++) { q[k] = c.pos[k]; q[3 + k] = c.frame[k]; }
+    q[6] = c.dist; q[7] = (float)c.g1; q[8] = (float)c.g2; q[9] = (float)c.dim;
+    o[TDBG_FORCE + ci] = L.nrow > 0 ? G.ef[c.row] : 0.f;
+  }
+}
+
+// env.reset() of the envs whose mask byte is set (NULL: all), then the FIRST observation is what the next step call reports
+__global__ void __launch_bounds__(64) k_tree_reset(const TreeModel* tm, const DevModel* gm, TreeTask T, TreeBuffers B, TreeEnvBuffers E, TreeStore S, const unsigned char* mask) {
+  BLOCK_SHARED(TreeLDS, L);
+  int e = blockIdx.x, lane = wave_lane(), N = T.n_envs;
+  if (mask && !mask[e]) return;
+  if (lane == 0) L.flags = 0;
+  wave_sync();
+  TreeScratch G = tree::scratch_of(B, e);
+  tree::env_reset(tm, gm, T, L, G, B, E, S, e);
+  tree::store_state(tm, L, B, e, N);
+  if (lane < tm->nu) B.ctrl[(size_t)lane * N + e] = L.ctrl[lane];
+  if (lane == 0) { E.need_reset[e] = 0; tree::store_diag(B, L, e); }
+}
+
+// placement + settle of episode `episode` of every env into row k of caller-owned tables (so101_tree_compute_settled): what env_reset()
+// would compute for that episode, without touching any env state
+__global__ void __launch_bounds__(64) k_tree_settle_table(const TreeModel* tm, const DevModel* gm, TreeTask T, TreeBuffers B, unsigned int episode, int k,
+                                                          float* qpos, float* qvel, float* warm, int* flags) {
+  BLOCK_SHARED(TreeLDS, L);
+  int e = blockIdx.x, lane = wave_lane(), N = T.n_envs;
+  if (lane == 0) L.flags = 0;
+  wave_sync();
+  TreeScratch G = tree::scratch_of(B, e);
+  tree::env_settle(tm, gm, T, L, G, e, episode);
+  size_t kk = (size_t)k;
+  if (lane < tm->nq) qpos[(kk * tm->nq + lane) * N + e] = L.qpos[lane];
+  if (lane < tm->nv) { qvel[(kk * tm->nv + lane) * N + e] = L.qvel[lane]; warm[(kk * tm->nv + lane) * N + e] = L.warm[lane]; }
+  if (lane == 0) flags[kk * N + e] = L.flags;
+}
+
+// Reset prefetch: the settled state of the NEXT episode of every env whose cache entry does not hold it yet (TreeStore, so101_tree.hpp), into
+// the library's cache, on a low-priority stream beside the stepping kernels; its own per-env scratch (B.scratch here is the second one)
+__global__ void __launch_bounds__(64) k_tree_prepare(const TreeModel* tm, const DevModel* gm, TreeTask T, TreeBuffers B, const int* episode_of, TreeStore S) {
+  BLOCK_SHARED(TreeLDS, L);
+  int e = blockIdx.x, lane = wave_lane(), N = T.n_envs;
+  unsigned int episode = (unsigned int)ld_agent(&episode_of[e]);
+  if (ld_agent(&S.ctag[e]) == episode + 1u) return;                                      // the entry is current
+  if (S.qpos && episode - (unsigned int)S.first < (unsigned int)S.count) return;          // the caller's settled-state store covers it
+  if (lane == 0) L.flags = 0;
+  wave_sync();
+  TreeScratch G = tree::scratch_of(B, e);
+  tree::env_settle(tm, gm, T, L, G, e, episode);
+  if (lane == 0) st_agent(&S.ctag[e], 0u);                                                 // (no reader may take a half-written entry for the old episode)
+  drain_stores();
+  if (lane < tm->nq) st_agent(&S.cq[(size_t)lane * N + e], L.qpos[lane]);
+  if (lane < tm->nv) { st_agent(&S.cv[(size_t)lane * N + e], L.qvel[lane]); st_agent(&S.cw[(size_t)lane * N + e], L.warm[lane]); }
+  if (lane == 0) st_agent(&S.cf[e], L.flags);
+  drain_stores();
+  wave_sync();
+  if (lane == 0) st_agent(&S.ctag[e], episode + 1u);
+}
+
+// settle the bound state with the one-dof joints held (dm_control's PropPlacer(settle_physics=True) alone, for callers that draw the
+// placements themselves): until |qvel| < 1e-3 and |qacc| < 1e-2 over the props' dofs or the budget ends (flag 32)
+__global__ void __launch_bounds__(64) k_tree_settle(const TreeModel* tm, const DevModel* gm, TreeTask T, TreeBuffers B) {
+  BLOCK_SHARED(TreeLDS, L);
+  int e = blockIdx.x, lane = wave_lane(), N = T.n_envs;
+  if (lane == 0) L.flags = 0;
+  tree::load_state(tm, L, B, e, N);
+  TreeScratch G = tree::scratch_of(B, e);
+  float q0 = lane < tm->njnt ? L.qpos[lane] : 0.f, v0 = lane < tm->njnt ? L.qvel[lane] : 0.f;
+  bool settled = T.settle_max == 0;
+  for (int k = 0; k < T.settle_max && !settled; k++) {
+    tree::forward(tm, gm, L, G, T.iterations, T.tolerance);
+    tree::euler(tm, L);
+    bool bad = tree::diverged(tm, L);       // (a named bool, as in tree::env_settle)
+    if (bad) { if (lane == 0) L.flags |= 8; break; }
+    if (lane < tm->njnt) { L.qpos[lane] = q0; L.qvel[lane] = v0; }
+    wave_sync();
+    float mv = 0.f, ma = 0.f;
+    if (lane >= tm->njnt && lane < tm->nv) { mv = fabsf(L.qvel[lane]); ma = fabsf(L.qacc[lane]); }
+    mv = wave_max_f(mv); ma = wave_max_f(ma);
+    settled = mv < 1e-3f && ma < 1e-2f;
+  }
+  if (!settled && lane == 0) L.flags |= 32;
+  tree::store_state(tm, L, B, e, N);
+  if (lane == 0 && B.diag) tree::store_diag(B, L, e);       // (B.diag tested here too: without it this kernel's register allocation changes)
+}
+
+// adopt the bound state as the post-reset state of a new episode (known-answer tests, checkpoints): delay lines filled with it,
+// counters cleared, no reset pending
+__global__ void __launch_bounds__(64) k_tree_begin(const TreeModel* tm, TreeTask T, TreeBuffers B, TreeEnvBuffers E) {
+  BLOCK_SHARED(TreeLDS, L);
+  int e = blockIdx.x, lane = wave_lane(), N = T.n_envs;
+  tree::load_state(tm, L, B, e, N);
+  tree::fill_delay_lines(tm, T, L, E, e);
+  if (lane == 0) { E.step_count[e] = 0; E.ep_return[e] = 0.f; E.need_reset[e] = 0; E.success_state[e] = T.requires_handover ? 0 : 2; }
+}
+
+// end of a control step of one env (after the last substep): observation, reward / discount / termination, state and counters out
+// CONTACTS: where the contact rewards take the contacts of the post-step state from - 0: not compiled (reward mode 0 only), 1: collision() in
+// place (single kernel), 2: gathered from the launch chain's records (k_tree_pipe_finish)
+template <int CONTACTS>
+__device__ __forceinline__ void tree_finish_step(const TreeModel* tm, const DevModel* gm, const TreeTask& T, TreeLDS& L, TreeScratch& G, const TreeBuffers& B,
+                                                 const TreeEnvBuffers& E, int e, bool diverged, float* obs, float* reward, float* discount, unsigned char* step_type,
+                                                 const TreePipe* P = nullptr) {
+  int lane = wave_lane(), N = T.n_envs;
+  if (diverged) {         // mj_check*: the data is reset, dm_control ends the episode with reward 0 and discount 0
+    if (lane < tm->nq) L.qpos[lane] = 0.f;
+    if (lane < tm->nv) { L.qvel[lane] = 0.f; L.warm[lane] = 0.f; }
+    wave_sync();
+    if (lane > 0 && lane < tm->nbody && tm->body_jnttype[lane] == TJ_FREE) L.qpos[tm->body_qposadr[lane] + 3] = 1.f;
+    if (lane == 0) L.flags |= 8;
+    wave_sync();
+  }
+  int sc = E.step_count[e] + 1;
+  tree::kinematics(tm, L);
+  tree::write_obs(T, L, E, e, sc, false, obs);
+  tree::write_physics_state(tm, T, L, E, e, sc);
+  // dm_control's Environment.step asks the task three times: get_reward, get_discount (-> should_terminate_episode -> get_reward) and
+  // should_terminate_episode (-> get_reward), aloha2_task.py:353-367.  For the overlap and touching rewards the three answers are the
+  // same; the contact sequence (hand_over.py:286-338) advances its state machine on EVERY call, so reward, discount and termination may
+  // each see a different state (0 -> 1 -> 2 and even the success within one control step).  Contacts: physics.data.contact after
+  // physics.step(), whose legacy step ends with mj_step1 - the contacts of the integrated state, recomputed here.
+  float r = 0.f, r_disc = 0.f, r_term = 0.f;
+  if (!diverged) {
+    if (CONTACTS == 0 || T.reward_mode == 0) r = r_disc = r_term = tree::task_reward(tm, T, L);
+    else if (T.reward_mode == 2) {
+      if constexpr (CONTACTS == 2) tree::gather_contacts(tm, gm, L, *P, e); else tree::collision(tm, gm, L);
+      r = r_disc = r_term = tree::task_reward_touching(tm, T, L);
+    } else {
+      if constexpr (CONTACTS == 2) tree::gather_contacts(tm, gm, L, *P, e); else tree::collision(tm, gm, L);
+      int st = E.success_state[e];
+      r = tree::task_reward_contacts(tm, T, L, G, &st);
+      if (T.terminate_on_success) { r_disc = tree::task_reward_contacts(tm, T, L, G, &st); r_term = tree::task_reward_contacts(tm, T, L, G, &st); }
+      if (lane == 0) E.success_state[e] = st;
+    }
+  }
+  bool disc0 = (T.terminate_on_success && r_disc >= 1.f) || diverged, success = (T.terminate_on_success && r_term >= 1.f) || diverged, timeout = sc >= T.last_step;
+  tree::store_state(tm, L, B, e, N);
+  if (lane < tm->nu) B.ctrl[(size_t)lane * N + e] = L.ctrl[lane];
+  if (lane == 0) {
+    reward[e] = r; discount[e] = disc0 ? 0.f : 1.f;
+    unsigned char st = (success || timeout) ? 2 : 1;
+    step_type[e] = st; E.need_reset[e] = st == 2;
+    E.step_count[e] = sc; E.ep_return[e] += r;
+    tree::store_diag(B, L, e);
+    if (B.diag) B.diag[8 * e + 5] = E.success_state[e];
+  }
+}
+
+// start of a control step of one env: an env whose last step was LAST resets and reports FIRST (returns true: done for this call);
+// the others load their state and apply the action
+__device__ __forceinline__ bool tree_begin_step(const TreeModel* tm, const DevModel* gm, const TreeTask& T, TreeLDS& L, TreeScratch& G, const TreeBuffers& B,
+                                                const TreeEnvBuffers& E, const TreeStore& S, int e, const float* action, float* obs, float* reward, float* discount,
+                                                unsigned char* step_type) {
+  int lane = wave_lane(), N = T.n_envs;
+  if (E.need_reset[e]) {
+    tree::env_reset(tm, gm, T, L, G, B, E, S, e);
+    tree::kinematics(tm, L);
+    tree::write_obs(T, L, E, e, 0, true, obs);
+    tree::store_state(tm, L, B, e, N);
+    if (lane < tm->nu) B.ctrl[(size_t)lane * N + e] = L.ctrl[lane];
+    if (lane == 0) { reward[e] = 0.f; discount[e] = 1.f; step_type[e] = 0; E.need_reset[e] = 0; }
+    if (lane == 0) tree::store_diag(B, L, e);
+    return true;
+  }
+  tree::load_state(tm, L, B, e, N);
+  // before_step (aloha2_task.py:316-349): joint targets as given, grippers from follower units to the sim's ctrl range; no clipping
+  if (lane < tm->nu) {
+    float a = action[(size_t)e * tm->nu + lane];
+    if (T.act_is_gripper[lane]) a = tree::convert_gripper(a, T.grip[4], T.grip[5], T.grip[2], T.grip[3]);
+    L.ctrl[lane] = a;
+  }
+  wave_sync();
+  return false;
+}
+
+// (The single-kernel step: N = 1, steps of more than 63 substeps, and the reference the launch chain below is tested against.  One wavefront per
+// SIMD: 458 unified registers, the hull caches and the EPA polytope of the inlined narrowphase among them.  __launch_bounds__(64, 2) was measured
+// in round 4 - 256 VGPRs, 770 spilled, 864 B of scratch per lane: 171 k against 175 k env-steps/s at 4096 envs.)
+// one control step of every env: dm_control's Environment.step - an env whose last step was LAST resets and reports FIRST
+// (the action is ignored), the others apply the action, run n_substeps and report observation, reward, discount, step type
+__global__ void __launch_bounds__(64) k_tree_step(const TreeModel* tm, const DevModel* gm, TreeTask T, TreeBuffers B, TreeEnvBuffers E, TreeStore S, const float* action,
+                                                  float* obs, float* reward, float* discount, unsigned char* step_type) {
+  BLOCK_SHARED(TreeLDS, L);
+  int e = blockIdx.x, lane = wave_lane(), N = T.n_envs;
+  if (lane == 0) L.flags = 0;
+  wave_sync();
+  TreeScratch G = tree::scratch_of(B, e);
+  if (tree_begin_step(tm, gm, T, L, G, B, E, S, e, action, obs, reward, discount, step_type)) return;
+  bool diverged = false;
+  for (int s = 0; s < T.n_substeps && !diverged; s++) {
+    tree::forward(tm, gm, L, G, T.iterations, T.tolerance);
+    tree::euler(tm, L);
+    diverged = tree::diverged(tm, L);
+  }
+  tree_finish_step<1>(tm, gm, T, L, G, B, E, e, diverged, obs, reward, discount, step_type);
+}
+
+#ifdef TREE_PROF
+__device__ unsigned long long g_tprof[33];     // (profiling variant: phase clocks of k_tree_pipe_solve summed over env-substeps, printed by destroy)
+#endif
+// ---- the control step as a launch chain (so101_tree.hpp, "the narrowphase in a launch of its own"): k_tree_pipe_begin, then per substep
+// k_tree_narrow and k_tree_pipe_solve.  Reward mode 0 (overlap boxes) only: the contact rewards need the contacts of the post-step state.
+__global__ void __launch_bounds__(64) k_tree_pipe_begin(const TreeModel* tm, const DevModel* gm, TreeTask T, TreeBuffers B, TreeEnvBuffers E, TreeStore S, TreePipe P,
+                                                        const float* action, float* obs, float* reward, float* discount, unsigned char* step_type, int e0) {
+  BLOCK_SHARED(TreeLDS, L);
+  int e = e0 + blockIdx.x, lane = wave_lane(), N = T.n_envs;
+  if (lane == 0) L.flags = 0;
+  wave_sync();
+  TreeScratch G = tree::scratch_of(B, e);
+  if (tree_begin_step(tm, gm, T, L, G, B, E, S, e, action, obs, reward, discount, step_type)) {
+    if (lane == 0) { P.active[e] = 0; P.ncand[e] = 0; }
+    return;
+  }
+  if (lane < tm->nu) B.ctrl[(size_t)lane * N + e] = L.ctrl[lane];
+  if (lane == 0) { P.active[e] = 1; P.pflags[e] = 0; }
+  tree::kinematics(tm, L);
+  tree::publish(tm, gm, L, P, e, N, 0);
+}
+
+// one wavefront per candidate pair of the whole batch: persistent wavefronts take two work items per fetch
+// (round 5: the hulls of a pair are staged in LDS - so101_geom.hpp, HullLDS - instead of held in 48 VGPRs; with the hull patches inlined the register
+//  cache left this kernel 55 spilled VGPRs and 184 B of scratch per lane)
+__global__ void __launch_bounds__(64, 2) k_tree_narrow(const TreeModel* tm, const DevModel* gm, TreePipe P, int N, int s) {
+  __shared__ __attribute__((aligned(16))) float pool[3 * 2 * HULL_LDS_MAX];
+  int lane = wave_lane();
+  const int nwork = ldc(&P.counters[2 * s]);
+  const unsigned int* list = P.work + (size_t)(s & 1) * P.work_cap;
+  for (;;) {
+    int i0 = 0;
+    if (lane == 0) i0 = atomicAdd(&P.counters[2 * s + 1], 2);
+    i0 = wave_uniform_i(i0);
+    if (i0 >= nwork) break;
+    unsigned int wl = 0, cl = 0;
+    if (lane < 2 && i0 + lane < nwork) { wl = list[i0 + lane]; cl = P.cand[wl]; }
+#pragma unroll 1
+    for (int j = 0; j < 2; j++) {
+      if (i0 + j >= nwork) break;
+      unsigned int w = (unsigned int)__builtin_amdgcn_readlane((int)wl, j), c = (unsigned int)__builtin_amdgcn_readlane((int)cl, j);
+      int e = (int)(w / TCAND), g1 = (int)(c & 0xffffu), g2 = (int)(c >> 16);
+      int b1 = wave_uniform_i(tm->geom_body[g1]), b2 = wave_uniform_i(tm->geom_body[g2]);
+      const float* p1 = P.pose + ((size_t)e * TB + b1) * 12; const float* p2 = P.pose + ((size_t)e * TB + b2) * 12;
+      GeomW G1, G2;
+      load_geom_at(gm, g1, p1, p1 + 3, G1); load_geom_at(gm, g2, p2, p2 + 3, G2);
+      PairContacts pc;
+      HullLDS H1{pool, hull_lds_slots(G1.type, G1.vnum)}, H2{pool + 3 * HULL_LDS_MAX, hull_lds_slots(G2.type, G2.vnum)};
+      wave_sync();                                     // (the scans of the previous pair are done)
+      hull_load(gm, G1, H1); hull_load(gm, G2, H2);
+      wave_sync();
+      narrow_pair_cached<HullLDS, G64>(gm, G1, G2, ldc(ldc(&gm->geom_rbound) + g1), ldc(ldc(&gm->geom_rbound) + g2), H1, H2, pc);
+      if (lane == 0) {
+        float* r = P.rec + (size_t)w * TREC;
+        r[0] = (float)__popc(pc.valid); r[1] = pc.nrm[0]; r[2] = pc.nrm[1]; r[3] = pc.nrm[2];
+        int o = 4;                                     // valid slots are written compactly, in slot order
+#pragma unroll
+        for (int q = 0; q < NCPP; q++)
+          if ((pc.valid >> q) & 1u) { r[o] = pc.dist[q]; r[o + 1] = pc.pos[q][0]; r[o + 2] = pc.pos[q][1]; r[o + 3] = pc.pos[q][2]; o += 4; }
+      }
+    }
+  }
+}
+
+__global__ void __launch_bounds__(64, TREE_SOLVE_OCC) k_tree_pipe_solve(const TreeModel* tm, const DevModel* gm, TreeTask T, TreeBuffers B, TreeEnvBuffers E, TreePipe P, int s, int last,
+                                                                       float* obs, float* reward, float* discount, unsigned char* step_type, int e0) {
+  BLOCK_SHARED(TreeLDS, L);
+  int e = e0 + blockIdx.x, lane = wave_lane(), N = T.n_envs;
+  int act = P.active[e];
+  if (act == 0) return;
+  if (lane == 0) L.flags = P.pflags[e];
+#ifdef TREE_PROF
+  if (lane < 32) L.prof[lane] = 0u;
+  wave_sync();
+#endif
+  TPROF_T0();
+  tree::load_state(tm, L, B, e, N);
+  TPROF(16)
+  TreeScratch G = tree::scratch_of(B, e);
+  bool diverged = act == 2;
+  if (!diverged) {
+    tree::forward_smooth(tm, L);
+    TPROF(12)
+    tree::gather_contacts(tm, gm, L, P, e);
+    TPROF(21)
+    tree::forward_constrained(tm, L, G, T.iterations, T.tolerance);
+    TPROF(13)
+    tree::euler(tm, L);
+    diverged = tree::diverged(tm, L);
+    if (diverged && lane == 0) P.active[e] = 2;
+    TPROF(22)
+  }
+  if (!last) {
+    if (act == 1) {
+      tree::store_state(tm, L, B, e, N);
+      if (lane == 0) tree::save_pipe_diag(P, L, e);
+      TPROF(23)
+      if (!diverged) {
+        tree::kinematics(tm, L);
+        TPROF(24)
+        tree::publish(tm, gm, L, P, e, N, s + 1);
+        TPROF(25)
+      }
+      else if (lane == 0) P.ncand[e] = 0;
+    }
+#ifdef TREE_PROF
+    wave_sync();
+    if (lane < 32) atomicAdd(&g_tprof[lane], (unsigned long long)L.prof[lane]);
+    if (lane == 0) atomicAdd(&g_tprof[32], 1ull);
+#endif
+    return;
+  }
+  if (act == 2) {
+    // diverged in an earlier substep: this launch computed nothing, the diagnostics are those of the last substep that was
+    if (lane == 0) tree::load_pipe_diag(P, L, e);
+    wave_sync();
+  }
+  tree_finish_step<0>(tm, gm, T, L, G, B, E, e, diverged, obs, reward, discount, step_type);
+}
+
+// end of a control step whose reward needs the contacts of the post-step state (reward modes 1 and 2): the last k_tree_pipe_solve published that
+// state's candidates like a substep's, k_tree_narrow has turned them into records
+__global__ void __launch_bounds__(64, 2) k_tree_pipe_finish(const TreeModel* tm, const DevModel* gm, TreeTask T, TreeBuffers B, TreeEnvBuffers E, TreePipe P,
+                                                            float* obs, float* reward, float* discount, unsigned char* step_type, int e0) {
+  BLOCK_SHARED(TreeLDS, L);
+  int e = e0 + blockIdx.x, lane = wave_lane(), N = T.n_envs;
+  int act = P.active[e];
+  if (act == 0) return;
+  if (lane == 0) { L.flags = P.pflags[e]; tree::load_pipe_diag(P, L, e); }
+  tree::load_state(tm, L, B, e, N);
+  TreeScratch G = tree::scratch_of(B, e);
+  tree_finish_step<2>(tm, gm, T, L, G, B, E, e, act == 2, obs, reward, discount, step_type, &P);
+}
+
+// ---- depth / segmentation cameras (so101_tree_render of include/so101.h): the frames kernel of this engine, one wavefront per rendered env.
+// It runs the engine's own kinematics on the qpos of the selected source - q[lane * lane_stride + e * env_stride]: the bound state
+// (qpos[nq][N], env-fastest) or the delayed physics-state line ([N][nq + nv], its first nq entries) - and publishes what k_render
+// (so101_raycast.hpp) consumes, record for record as k_render_frames (so101_camera.hpp) does for SO100: per geom the world frame of
+// load_geom_at(), the bounding-sphere centre and geom_rbound (-1: the env index is outside [0, N), nothing of that image can be hit), per
+// camera its world frame.  A camera is fixed to the world (body -1 or 0: kinematics() keeps the identity there) or to a tree body.
+__global__ void __launch_bounds__(64) k_tree_render_frames(const TreeModel* tm, const DevModel* gm, const float* q, size_t lane_stride, size_t env_stride, int N,
+                                                           const int* env_index, RenderCams cams, int ncam, float* frames, float* camframes) {
+  BLOCK_SHARED(TreeLDS, L);
+  const int i = blockIdx.x, lane = wave_lane();
+  int e = env_index ? env_index[i] : i;
+  e = wave_uniform_i(e);
+  const bool ok = e >= 0 && e < N;
+  if (lane < tm->nq) L.qpos[lane] = q[(size_t)lane * lane_stride + (size_t)(ok ? e : 0) * env_stride];
+  wave_sync();
+  tree::kinematics(tm, L);
+  const int ngeom = gm->ngeom;
+  for (int g = lane; g < ngeom; g += WAVE) {
+    int b = gm->geom_dyn[g];            // (this engine's geom_dyn is the body id)
+    GeomW G;
+    load_geom_at<G16>(gm, g, L.xpos[b], L.xmat[b], G);
+    float* f = frames + ((size_t)i * ngeom + g) * RENDER_FRAME;
+#pragma unroll
+    for (int k = 0; k < 9; k++) f[k] = G.R[k];
+#pragma unroll
+    for (int k = 0; k < 3; k++) { f[9 + k] = G.p[k]; f[12 + k] = G.c[k]; }
+    f[15] = ok ? gm->geom_rbound[g] : -1.f;
+  }
+  // cameras: composed with their body's pose on wave-uniform values (constant indices into the kernel argument), lane 0 publishes
+#pragma unroll
+  for (int k = 0; k < RENDER_MAXCAM; k++) {
+    if (k >= ncam) break;
+    const int b = cams.cam[k].body < 0 ? 0 : cams.cam[k].body;
+    float X[9], P0[3], cp[3], cm[9];
+#pragma unroll
+    for (int j = 0; j < 9; j++) { X[j] = L.xmat[b][j]; cm[j] = cams.cam[k].mat[j]; }
+#pragma unroll
+    for (int j = 0; j < 3; j++) { P0[j] = L.xpos[b][j]; cp[j] = cams.cam[k].pos[j]; }
+    float t[3], M[9]; matvec3(t, X, cp); matmul3(M, X, cm);
+    if (lane == 0) {
+      float* f = camframes + ((size_t)i * ncam + k) * RENDER_CAMFRAME;
+#pragma unroll
+      for (int j = 0; j < 3; j++) f[j] = P0[j] + t[j];
+#pragma unroll
+      for (int j = 0; j < 9; j++) f[3 + j] = M[j];
+      f[12] = cams.cam[k].scale;
+    }
+  }
+}
+}  // namespace TREE_NS

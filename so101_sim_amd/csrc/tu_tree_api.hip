@@ -1,5 +1,5 @@
 // Public entry points of the general-tree engine (include/so101.h, so101_tree_*): a handle names one of the two builds of
-// csrc/so101_tree.hpp - 32 dofs / 128 geoms / 64 contacts (tu_tree.hip: the ALOHA hand-over scenes) or 64 dofs / 256 geoms / 128 contacts
+// csrc/so101_tree.hpp (with its kernels, so101_tree_kernels.hpp, and host code, so101_tree_host.hpp) - 32 dofs / 128 geoms / 64 contacts (tu_tree.hip: the ALOHA hand-over scenes) or 64 dofs / 256 geoms / 128 contacts
 // (tu_tree64.hip: the Dining scenes) - chosen by so101_tree_create from the model's dimensions; every other call forwards.
 #include <cstddef>
 #include <cstdint>

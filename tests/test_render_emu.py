@@ -11,6 +11,9 @@ from tests import raycast_ref as rr
 from tests.render_cases import JAW_CAM, render, scene_planes
 from tests.simharness import ArraySim
 
+# what commit f55d392 (the last one whose two engines each counted and grew their own render buffers) reports for the sequence of
+# test_scratch_bytes_count_the_planes_and_the_grown_frames_scratch, measured with that commit's library under the emulator
+SCRATCH_BYTES_AFTER_RENDERS = 1043419
 
 def _check_planes(verts, planes):
     assert planes.dtype == np.float64 and planes.shape[1] == 4 and len(planes) >= 4
@@ -106,6 +109,19 @@ def test_plane_validation_and_render_state_errors(blobs):
     cam[0].body, cam[0].fovy_deg = -1, 180.0
     assert call() == -1
     assert L.so101_render(None, cam, 1, 4, 4, None, 1, None, None, None) == -1
+
+
+def test_scratch_bytes_count_the_planes_and_the_grown_frames_scratch(blobs):
+    """create, set_hull_planes, a render of 2 envs, then one of 5 (the frames scratch is freed and allocated again): SO101_INFO_SCRATCH_BYTES
+    counts the planes once and the scratch of 5 envs, not of 2 + 5"""
+    sim = ArraySim(blobs["f32"], 5, backend="emu")
+    sim.sim.set_hull_planes(*scene_planes(blobs["f32"]))
+    sim.set_state(np.tile(rr.STATES["grasp"][:, None], (1, 5)))
+    cams = [cameras.SO100_CAMERAS["overhead_cam"]]
+    render(sim, cams, 4, 4, env_index=[0, 1])
+    render(sim, cams, 4, 4)
+    print("scratch_bytes", sim.sim.info()["scratch_bytes"])
+    assert sim.sim.info()["scratch_bytes"] == SCRATCH_BYTES_AFTER_RENDERS
 
 
 def test_emulated_render_matches_fp64_reference(blobs):
