@@ -338,6 +338,52 @@ int so101_tool_pose(so101_sim* sim, const so101_tool* tool, const float* q, cons
 int so101_tool_ik(so101_sim* sim, const so101_tool* tool, const so101_ik_config* cfg, const float* target_pos, const float* target_mat,
                   const float* q_init, const int32_t* env_index, int n, float* q_out, float* residual, int32_t* info, void* hip_stream);
 
+/* ---- contact sensing (csrc/so101_contacts.hpp): the contact list of an env's CURRENT bound state (qpos, qvel, ctrl, warmstart) and its reduction
+ * over pairs of geom groups, for thousands of envs per call on the device.  Stands in for physics.data.contact / physics.data.ncon and the
+ * reference tasks' _touching(geoms_a, geoms_b) loops over it (so100_hand_over.py:291-313), and with forces != 0 for mujoco.mj_contactForce.  The
+ * pass is mj_forward at the bound state cut down to the report: kinematics and collision for the geometry; with forces != 0 also the mass
+ * matrix, the smooth dynamics, the constraint rows and the configured solver (the iterations, tolerance and warmstart of so101_debug_forward) -
+ * with forces == 0 none of that runs.  So the forces are those of a forward pass at the current state, NOT the impulses of the last substep.
+ * SO100 engine only; additions: the ABI number stays.
+ *
+ * A group is a 128-bit mask over geoms; a contact belongs to pair (a, b) if one of its geoms is in a and the other in b.  The order
+ * "geom1 in a, geom2 in b" is tried first, "geom2 in a, geom1 in b" second: a contact for which both hold (overlapping groups) counts once,
+ * with the sign of the first.  pair_force: with R the contact's frame (rows) and f its force, the constraint force acts on geom2's body along
+ * the normal from geom1 to geom2, so the contact adds +R^T f[0:3] when group A holds geom2 and -R^T f[0:3] when it holds geom1: the net
+ * world-frame force ON group A.  Swapping a and b negates pair_force (bit for bit when no contact holds both orders) and changes nothing else.
+ *
+ * The list is the step's: at most so101_max_contacts() contacts per env, in the step's order; an env with more keeps one contact per touching
+ * geom pair (the capacity rule of event 7).  flags = diag word 4 of THIS pass: 1 candidate overflow, 2 contact overflow, 128 reduced to one
+ * contact per pair (with forces != 0 also what the solve raises).  frame is the full MuJoCo contact.frame; force is the contact's force in that
+ * frame, the entries beyond its dim zero (csrc/so101_contacts.hpp says where both are read).  Slots at or beyond count: geoms -1, dist +inf,
+ * the other floats 0.  An env_index entry outside the batch reads nothing: count -1, flags 0, geoms -1, pair_count 0, every float output NaN
+ * (the convention of so101_tool_pose).  An entry's output bits depend on its env's state, forces, the solver settings and (the pair outputs)
+ * its pair only - not on n or the other entries.  Asynchronous on `hip_stream`, changes no state - the warmstart included.
+ *
+ * env_index: DEVICE array of n env indices, or NULL for envs 0 .. n - 1.  pairs: HOST array of npair pairs, copied.  out: HOST struct of
+ * DEVICE pointers.  SO101_ERR_ARG (with a message in so101_last_error): NULL handle or out; no output pointer at all; n outside 1 .. 2^26, or
+ * n > n_envs with env_index == NULL; npair outside 0 .. SO101_TOUCH_MAX_PAIRS; npair > 0 with NULL pairs; a pair output with npair == 0; an
+ * empty group; a group bit at or beyond ngeom; force, pair_normal or pair_force with forces == 0.  SO101_ERR_STATE: no state bound, or a
+ * model with more than 128 geoms. */
+#define SO101_TOUCH_MAX_PAIRS 16
+typedef struct { uint32_t a[4], b[4]; } so101_geom_pair;   /* bit (g & 31) of word g >> 5: geom g belongs to the group; ngeom <= 128 */
+typedef struct {
+  int32_t* count;        /* [n]        contacts of the env, -1 for an env_index outside the batch */
+  int32_t* flags;        /* [n]        the overflow bits of diag word 4 for THIS pass (candidate overflow, contact overflow, reduced to one per pair) */
+  int32_t* geom;         /* [n][C][2]  geom1, geom2;  C = so101_max_contacts() */
+  float*   dist;         /* [n][C] */
+  float*   pos;          /* [n][C][3] */
+  float*   frame;        /* [n][C][9]  rows: normal (geom1 -> geom2), tangent 1, tangent 2: MuJoCo's contact.frame */
+  float*   force;        /* [n][C][6]  mj_contactForce: the contact's force in its frame, entries beyond its dim zero; needs forces != 0 */
+  int32_t* pair_count;   /* [n][npair] */
+  float*   pair_dist;    /* [n][npair] minimum dist, +inf without a contact */
+  float*   pair_normal;  /* [n][npair] sum of f[0]; needs forces */
+  float*   pair_force;   /* [n][npair][3] world frame, the force ON group A; needs forces */
+} so101_contact_out;       /* DEVICE pointers, any may be NULL, not all */
+int so101_contacts(so101_sim* sim, const int32_t* env_index, int n, int forces,
+                   const so101_geom_pair* pairs /* HOST, npair of them */, int npair,
+                   const so101_contact_out* out, void* hip_stream);
+
 const char* so101_last_error(const so101_sim* sim);
 
 /* ---- general-tree engine (csrc/so101_tree.hpp): models outside the SO100 topology - the ALOHA hand-over scenes of

@@ -26,6 +26,9 @@ void launch_step(int solver, int n_envs, hipStream_t st, const DevModel* m, cons
 void launch_physics(int solver, int n_envs, hipStream_t st, const DevModel* m, const StepParams& P, const DevBuffers& B,
                     int nsub, int freeze, int* diag);
 void launch_debug_forward(int solver, int n_envs, hipStream_t st, const DevModel* m, const StepParams& P, const DevBuffers& B, float* out);
+// contact sensing (so101_contacts.hpp): one wavefront per reported env, n of them; env_index NULL = envs 0 .. n - 1
+void launch_contacts(int solver, int n, hipStream_t st, const DevModel* m, const StepParams& P, const DevBuffers& B, const int* env_index, int forces,
+                     const TouchPairs& T, const ContactOut& O);
 void launch_begin(int n_envs, hipStream_t st, const DevModel* m, const StepParams& P, const DevBuffers& B, unsigned char* need_reset);
 void launch_reward(int n_envs, hipStream_t st, const DevModel* m, const StepParams& P, const DevBuffers& B, float* reward);
 
@@ -73,5 +76,7 @@ void launch_step_pgs(int n_envs, hipStream_t st, const DevModel* m, const StepPa
                      const EventBuffers& E, const StepIO& io, unsigned char* need_reset, int* diag);
 void launch_physics_pgs(int n_envs, hipStream_t st, const DevModel* m, const StepParams& P, const DevBuffers& B, int nsub, int freeze, int* diag);
 void launch_debug_forward_pgs(int n_envs, hipStream_t st, const DevModel* m, const StepParams& P, const DevBuffers& B, float* out);
+void launch_contacts_pgs(int n, hipStream_t st, const DevModel* m, const StepParams& P, const DevBuffers& B, const int* env_index, int forces,
+                         const TouchPairs& T, const ContactOut& O);
 
 }  // namespace so101

@@ -293,3 +293,16 @@ struct ChainParams { const DevModel* m; StepParams P; DevBuffers B; EventBuffers
 #define RENDER_CAMFRAME 13       // floats per camera: pos[3], mat[9] (world from camera; columns x right, y up, z; the camera looks along -z), pixel scale
 struct RenderCam { int body; float pos[3], mat[9], scale; };      // body: -1 world, else as geom_dyn numbers the bodies (SO100: 0 .. NDYN - 1, tree: the body id); scale = 2 tan(fovy / 2) / H
 struct RenderCams { RenderCam cam[RENDER_MAXCAM]; };
+
+// ---- contact sensing (so101_contacts.hpp): the geom-group pairs of one so101_contacts call (a kernel argument) and its outputs
+#define TOUCH_MAX_PAIRS 16        // SO101_TOUCH_MAX_PAIRS of include/so101.h
+struct TouchPairs {               // bit (g & 31) of word g >> 5: geom g belongs to the group
+  int npair;
+  unsigned int a[TOUCH_MAX_PAIRS][4], b[TOUCH_MAX_PAIRS][4];
+};
+struct ContactOut {               // so101_contact_out: device pointers, any may be NULL
+  int *count, *flags, *geom;
+  float *dist, *pos, *frame, *force;
+  int* pair_count;
+  float *pair_dist, *pair_normal, *pair_force;
+};

@@ -1,6 +1,7 @@
-// Translation unit: physics-only stepping, the parity-test stage dump, reward, episode bookkeeping (Newton), the cameras, Cartesian tool control
+// Translation unit: physics-only stepping, the parity-test stage dump, contact sensing, reward, episode bookkeeping (Newton), the cameras, Cartesian tool control
 // of both engines (the chain kernels for 6 columns - SO100 - and 8 - the general-tree engine, both builds).
 #include "so101_kernels.hpp"
+#include "so101_contacts.hpp"
 #include "so101_camera.hpp"
 #include "so101_tool_chain.hpp"
 #include "so101_launch.hpp"
@@ -38,6 +39,11 @@ void launch_physics(int solver, int n_envs, hipStream_t st, const DevModel* m, c
 void launch_debug_forward(int solver, int n_envs, hipStream_t st, const DevModel* m, const StepParams& P, const DevBuffers& B, float* out) {
   if (solver == 0) { launch_debug_forward_pgs(n_envs, st, m, P, B, out); return; }
   hipLaunchKernelGGL(k_debug_forward<1>, dim3(n_envs), dim3(64), 0, st, m, P, B, out);
+}
+void launch_contacts(int solver, int n, hipStream_t st, const DevModel* m, const StepParams& P, const DevBuffers& B, const int* env_index, int forces,
+                     const TouchPairs& T, const ContactOut& O) {
+  if (solver == 0) { launch_contacts_pgs(n, st, m, P, B, env_index, forces, T, O); return; }
+  hipLaunchKernelGGL(k_contacts<1>, dim3((unsigned int)n), dim3(64), 0, st, m, P, B, env_index, forces, T, O);
 }
 void launch_begin(int n_envs, hipStream_t st, const DevModel* m, const StepParams& P, const DevBuffers& B, unsigned char* need_reset) {
   hipLaunchKernelGGL(k_begin, dim3(n_envs), dim3(64), 0, st, m, P, B, need_reset);

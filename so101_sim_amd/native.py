@@ -32,7 +32,7 @@ EXPORTS = (
     "so101_version", "so101_max_contacts", "so101_create", "so101_destroy", "so101_default_config",
     "so101_configure", "so101_bind_state", "so101_bind_physics_state", "so101_set_reset_pool", "so101_compute_settled", "so101_set_settled_store", "so101_reset", "so101_settle", "so101_begin_episode", "so101_step", "so101_physics", "so101_reward",
     "so101_get_returns", "so101_get_diag", "so101_get_events", "so101_debug_forward", "so101_debug_candidates", "so101_debug_stages", "so101_get_info", "so101_debug_chain_stats", "so101_last_error",
-    "so101_set_hull_planes", "so101_render", "so101_ik_default_config", "so101_tool_pose", "so101_tool_ik",
+    "so101_set_hull_planes", "so101_render", "so101_ik_default_config", "so101_tool_pose", "so101_tool_ik", "so101_contacts",
     "so101_tree_create", "so101_tree_destroy", "so101_tree_dims", "so101_tree_last_plan", "so101_tree_bind_state", "so101_tree_configure", "so101_tree_physics",
     "so101_tree_debug_forward", "so101_tree_get_diag", "so101_tree_last_error", "so101_tree_obs_dim", "so101_tree_bind_env",
     "so101_tree_configure_env", "so101_tree_bind_physics_state", "so101_tree_reset", "so101_tree_step", "so101_tree_set_hull_planes", "so101_tree_render", "so101_tree_begin_episode", "so101_tree_settle", "so101_tree_compute_settled", "so101_tree_set_settled_store",
@@ -85,6 +85,29 @@ class TreeIkConfig(C.Structure):
     """so101_tree_ik_config of include/so101.h"""
     _fields_ = [("mode", C.c_int32), ("max_iters", C.c_int32), ("tol_pos", C.c_float), ("tol_rot", C.c_float), ("rot_weight", C.c_float),
                 ("damping", C.c_float), ("max_step", C.c_float), ("free_mask", C.c_uint32), ("q_lo", C.c_float * 8), ("q_hi", C.c_float * 8)]
+
+
+TOUCH_MAX_PAIRS = 16          # SO101_TOUCH_MAX_PAIRS
+CONTACT_OUT_FIELDS = ("count", "flags", "geom", "dist", "pos", "frame", "force", "pair_count", "pair_dist", "pair_normal", "pair_force")
+
+
+class GeomPair(C.Structure):
+    """so101_geom_pair of include/so101.h: two 128-bit geom masks"""
+    _fields_ = [("a", C.c_uint32 * 4), ("b", C.c_uint32 * 4)]
+
+
+class ContactOut(C.Structure):
+    """so101_contact_out of include/so101.h: raw device addresses, None = not wanted"""
+    _fields_ = [(k, C.c_void_p) for k in CONTACT_OUT_FIELDS]
+
+
+def geom_pair_array(pairs):
+    """((a words[4], b words[4]), ...) as the so101_geom_pair array of so101_contacts"""
+    arr = (GeomPair * max(len(pairs), 1))()
+    for k, (a, b) in enumerate(pairs):
+        arr[k].a[:] = [int(x) & 0xFFFFFFFF for x in a]
+        arr[k].b[:] = [int(x) & 0xFFFFFFFF for x in b]
+    return arr
 
 
 TREE_TOOL_MAXCOL = 8          # columns of a tool's chain at most (so101_tree_tool_chain)
@@ -154,6 +177,7 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.so101_ik_default_config.argtypes = [vp, C.POINTER(IkConfig)]
     L.so101_tool_pose.argtypes = [vp, C.POINTER(ToolSpec), vp, vp, C.c_int, vp, vp, vp, vp]
     L.so101_tool_ik.argtypes = [vp, C.POINTER(ToolSpec), C.POINTER(IkConfig), vp, vp, vp, vp, C.c_int, vp, vp, vp, vp]
+    L.so101_contacts.argtypes = [vp, vp, C.c_int, C.c_int, C.POINTER(GeomPair), C.c_int, C.POINTER(ContactOut), vp]
     _libs[path] = L
     return L
 
@@ -306,6 +330,11 @@ class Sim:
         """so101_tool_ik; cfg from ik_config(); the arrays are raw device addresses or None"""
         self._check(self.L.so101_tool_ik(self.h, C.byref(tool_spec(tool)), C.byref(cfg), target_pos, target_mat, q_init, env_index, int(n),
                                          q_out, residual, info, stream), "so101_tool_ik")
+
+    def contacts(self, env_index, n: int, forces: bool, pairs, out: ContactOut, stream=0):
+        """so101_contacts; pairs: sequence of (a words[4], b words[4]) geom masks; env_index and the fields of `out`: raw device addresses or None"""
+        arr = geom_pair_array(pairs) if pairs else None
+        self._check(self.L.so101_contacts(self.h, env_index, int(n), int(bool(forces)), arr, len(pairs) if pairs else 0, C.byref(out), stream), "so101_contacts")
 
 
 class TreeConfig(C.Structure):
