@@ -344,7 +344,7 @@ int so101_tool_ik(so101_sim* sim, const so101_tool* tool, const so101_ik_config*
  * pass is mj_forward at the bound state cut down to the report: kinematics and collision for the geometry; with forces != 0 also the mass
  * matrix, the smooth dynamics, the constraint rows and the configured solver (the iterations, tolerance and warmstart of so101_debug_forward) -
  * with forces == 0 none of that runs.  So the forces are those of a forward pass at the current state, NOT the impulses of the last substep.
- * SO100 engine only; additions: the ABI number stays.
+ * SO100 engine; so101_tree_contacts below is the general-tree engine's.  Additions: the ABI number stays.
  *
  * A group is a 128-bit mask over geoms; a contact belongs to pair (a, b) if one of its geoms is in a and the other in b.  The order
  * "geom1 in a, geom2 in b" is tried first, "geom2 in a, geom1 in b" second: a contact for which both hold (overlapping groups) counts once,
@@ -390,7 +390,7 @@ const char* so101_last_error(const so101_sim* sim);
  * so101_sim/tasks/hand_over.py (two 8-dof arms with slide fingers coupled by joint equalities, position actuators, joint
  * damping; reference model so101_sim/assets/aloha/aloha_pbr.xml).  The blob is the f32 blob of
  * so101_sim_amd.model.scenes.compile_aloha_scene / compile_dining_scene; limits: 32 bodies, 16 actuators and, per build, 32 dofs /
- * 128 geoms / 64 contacts / 384 rows (ALOHA hand-over) or 64 dofs / 256 geoms / 128 contacts / 768 rows (Dining).
+ * 128 geoms / 64 contacts / 384 rows (ALOHA hand-over) or 64 dofs / 256 geoms / 160 contacts / 960 rows (Dining).
  * Physics entry points only so far (what dm_control's physics.step() does for these scenes); same conventions as above:
  * device pointers, env-fastest struct-of-arrays state [dim][n_envs], asynchronous on `hip_stream`. */
 typedef struct so101_tree so101_tree;
@@ -399,7 +399,7 @@ void so101_tree_destroy(so101_tree* sim);
 /* dims[16] = nq, nv, nu, nbody, ngeom, floats per env of so101_tree_debug_forward, contact capacity; then the layout of that row for the
  * handle's build - offsets of bias, qacc_smooth, qacc, body positions, mass matrix, contacts, normal forces, the row stride of the mass
  * matrix - and the build itself (32 or 64: so101_tree_create takes the 32-dof / 128-geom / 64-contact build whenever the model fits it,
- * otherwise the 64-dof / 256-geom / 128-contact one of the Dining scenes) */
+ * otherwise the 64-dof / 256-geom / 160-contact one of the Dining scenes) */
 int so101_tree_dims(const so101_tree* sim, int* dims);
 /* What the last so101_tree_step of this handle enqueued, as the library counted it (not a host-side copy of the rule): out[4] = env slices,
  * kernel launches, memsets, path (0: no step yet, 1: the single kernel k_tree_step, 2: the launch chain).  bench.py reports it as evidence. */
@@ -524,6 +524,33 @@ int so101_tree_tool_pose(so101_tree* sim, const so101_tree_tool* tool, const flo
  * so101_tool_ik on the configuration (q_lo <= q_hi over the chain's columns), and free_mask bits at or above ncol. */
 int so101_tree_tool_ik(so101_tree* sim, const so101_tree_tool* tool, const so101_tree_ik_config* cfg, const float* target_pos, const float* target_mat,
                        const float* q_init, const int32_t* env_index, int n, float* q_out, float* residual, int32_t* info, void* hip_stream);
+/* ---- contact sensing of this engine (csrc/so101_tree_contacts.hpp): so101_contacts above on a tree handle, for both builds - the same semantics
+ * and conventions with this engine's stages and capacity.  The pass is so101_tree_debug_forward's cut down to the report: kinematics and collision for
+ * the geometry; with forces != 0 also the mass matrix, the bias forces, the smooth dynamics, the constraint rows and the Newton solve with the handle's
+ * iterations and tolerance (so101_tree_configure) - with forces == 0 none of that runs.  Its numbers are so101_tree_debug_forward's bit for bit.
+ * Stands in for looping over physics.data.contact in the contact-sequence reward (hand_over.py:286-338) and the Dining `contact` reward
+ * (dining_place_in_container.py:126-154), and with forces for mujoco.mj_contactForce.
+ *
+ * so101_contact_out is reused unchanged with C = the handle's contact capacity, dims[6] of so101_tree_dims (64 or 160).  A group is a 256-bit mask
+ * over geoms, in both builds.  Pair membership, the order rule ("geom1 in a, geom2 in b" first; a contact holding both orders counts once, with the
+ * sign of the first), the sign of pair_force (the net world-frame force ON group A), the fill values of slots at or beyond count (geoms -1, dist
+ * +inf, the other floats 0) and the convention for an env_index entry outside the batch (count -1, flags 0, geoms -1, pair_count 0, every float NaN)
+ * are those of so101_contacts.
+ *
+ * The capacity rule is THIS engine's: the list is the step's, in the step's order, and it ENDS at the first candidate pair whose contacts do not fit
+ * the capacity (flag 2) - there is no reduction to one contact per pair.  flags = the engine's flag word of THIS pass, started at 0: 1 candidate
+ * overflow, 2 contact overflow, and with forces != 0 also 4: the constraint rows of the last contacts did not fit the row capacity and those contacts
+ * were left out of the solve.  count and the per-contact geometry are always those of the collision stage, so the geometry is the same bit for bit
+ * with and without forces; a contact that got no rows reports zero force and adds nothing to pair_normal / pair_force.
+ *
+ * An entry's output bits depend on its env's state, forces, the solver settings and (the pair outputs) its pair only - not on n or the other entries;
+ * env_index may name an env more than once.  Asynchronous on `hip_stream` (with forces != 0 as ceil(n / n_envs) launches), changes no state - the
+ * warmstart included.  env_index: DEVICE, or NULL for envs 0 .. n - 1; pairs: HOST, copied; out: HOST struct of DEVICE pointers.  SO101_ERR_ARG with
+ * the messages of so101_contacts under the name so101_tree_contacts (ngeom is the handle's, dims[4]); SO101_ERR_STATE: no state bound. */
+typedef struct { uint32_t a[8], b[8]; } so101_tree_geom_pair;   /* 256-bit groups, bit (g & 31) of word g >> 5; both builds take this struct */
+int so101_tree_contacts(so101_tree* sim, const int32_t* env_index, int n, int forces,
+                        const so101_tree_geom_pair* pairs /* HOST, npair of them */, int npair,
+                        const so101_contact_out* out, void* hip_stream);
 const char* so101_tree_last_error(const so101_tree* sim);
 
 #ifdef __cplusplus

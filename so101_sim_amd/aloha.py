@@ -12,6 +12,8 @@ Cameras: `render_depth` casts the scene's six cameras (cameras.ALOHA_CAMERAS) or
 on the GPU (so101_tree_render) - depth and geom ids, from the current or the delayed state; not RGB, and not wired into the observation.
 Cartesian tool control: `tool_pose`, `tool_chain`, `solve_ik` and `cartesian_action` give the pose and Jacobian of the six tool sites
 (tools.ALOHA_TOOLS) or any tools.Tool and the joint values that bring one to a target, batched on the GPU (so101_tree_tool_pose / so101_tree_tool_ik).
+Contact sensing: `contacts`, `touch` and `geom_group` give the contact list of the current state (64 contacts per env in the hand-over scenes, 160 in
+Dining) and "who touches whom" over pairs of geom groups (contacts.aloha_groups), batched on the GPU (so101_tree_contacts).
 Not built: a non-default table height offset (the committed model blob is compiled for the reference's default).  The observation delays ARE parameters (`joints_observation_delay_secs`, `image_observation_delay_secs`,
 aloha2_task.py:153-159: whole control steps, handed to the kernels by so101_tree_configure_env), and `physics_state` /
 `delayed_physics_state` come from a device-side delay line (so101_tree_bind_physics_state).  Both reward modes are built: the overlap boxes (default) and the contact sequence
@@ -527,6 +529,65 @@ class AlohaEnvironment(ToolControl):
             if g is not None:
                 action[:, a] = self._f32(g)
         return action
+
+    # ------------------------------------------------------------------ contact sensing (contacts.py)
+    def _geom_groups(self):
+        from . import contacts as _contacts
+        if getattr(self, "_groups", None) is None:
+            self._groups = _contacts.aloha_groups(self.meta, blobfmt.unpack(self.task.load_blob("f32")[0]))
+        return self._groups
+
+    def geom_group(self, spec):
+        """A contacts.GeomGroup from a group name of the scene (contacts.aloha_groups: every body name, "left_arm", "right_arm", "arms",
+        "left_gripper", "right_gripper", "grippers", "object", "container", "props"), a geom name, an fnmatch pattern over the geom names, an
+        iterable of geom ids or a GeomGroup.  ALOHA geom names are not unique (`vx300s_8_custom_finger_left` occurs once per arm): a geom
+        name or a pattern resolves to ALL geoms that match."""
+        from . import contacts as _contacts
+        return _contacts.resolve(spec, self._geom_groups(), self.meta, limit=_contacts.TREE_MAX_GEOMS)
+
+    def contacts(self, env_ids=None, forces: bool = False):
+        """The contact lists of the envs `env_ids` (None = all) at their current state, on the GPU (so101_tree_contacts): a
+        contacts.ContactReport of tensors on the env's device - count [n], flags [n] (1 candidate overflow, 2 contact overflow: the list ends at
+        the first geom pair that does not fit the C contacts, 4 with forces: the rows of the last contacts did not fit, they report zero force),
+        geom [n, C, 2], dist [n, C], pos [n, C, 3], frame [n, C, 3, 3] (rows: normal geom1 -> geom2 and two tangents, MuJoCo's contact.frame) and,
+        with forces=True, force [n, C, 6] (mj_contactForce), else None; C = 64 in the hand-over scenes, 160 in Dining (`sim.max_contacts`).
+        Slots beyond count hold geoms -1, dist +inf, zeros.  The forces are those of a forward pass at the current state (constraint rows and
+        solve, warmstart read and left alone), not the impulses of the last substep; without forces only kinematics and collision run.
+        There is no `physics` facade on this environment: `contacts.records(report, entry)` gives the list of `physics.data.contact`-like
+        records of one entry."""
+        from . import contacts as _contacts
+        torch = self.torch
+        idx, n = self._env_index(env_ids)
+        C = self.sim.max_contacts
+        e = lambda *s, dt=torch.float32: torch.empty(*s, dtype=dt, device=self.device)
+        rep = _contacts.ContactReport(e(n, dt=torch.int32), e(n, dt=torch.int32), e(n, C, 2, dt=torch.int32), e(n, C), e(n, C, 3), e(n, C, 3, 3),
+                                      e(n, C, 6) if forces else None)
+        out = native.ContactOut(**{k: (t.data_ptr() if t is not None else None) for k, t in rep._asdict().items()})
+        self.sim.contacts(idx.data_ptr() if idx is not None else None, n, forces, None, out, self._stream())
+        return rep
+
+    def touch(self, pairs, env_ids=None, forces: bool = False):
+        """Who touches whom: `pairs` is a sequence of at most 16 (a, b), each side anything geom_group() takes.  Per env of `env_ids` (None = all)
+        and pair, reduced on the GPU from the env's contact list: a contacts.TouchReport of count [n, npair] int32 (contacts with one geom in a
+        and the other in b), touching = count > 0, dist [n, npair] (the smallest, +inf without a contact) and, with forces=True,
+        normal_force [n, npair] (sum of the normal forces) and force [n, npair, 3] (the net world-frame force ON group a), else None.
+        `("right_gripper", "object")`, `("left_gripper", "object")` and `("object", "container")` are the questions of the contact-sequence
+        reward (hand_over.py:286-338), the last one that of the Dining `contact` reward."""
+        from . import contacts as _contacts
+        torch = self.torch
+        pairs = list(pairs)
+        if not 1 <= len(pairs) <= _contacts.MAX_PAIRS:
+            raise ValueError(f"touch takes 1 .. {_contacts.MAX_PAIRS} pairs, got {len(pairs)}")
+        masks = [(self.geom_group(a).mask(8), self.geom_group(b).mask(8)) for a, b in pairs]
+        idx, n = self._env_index(env_ids)
+        P = len(masks)
+        e = lambda *s, dt=torch.float32: torch.empty(*s, dtype=dt, device=self.device)
+        count, dist = e(n, P, dt=torch.int32), e(n, P)
+        normal, force = (e(n, P), e(n, P, 3)) if forces else (None, None)
+        out = native.ContactOut(pair_count=count.data_ptr(), pair_dist=dist.data_ptr(), pair_normal=normal.data_ptr() if forces else None,
+                                pair_force=force.data_ptr() if forces else None)
+        self.sim.contacts(idx.data_ptr() if idx is not None else None, n, forces, masks, out, self._stream())
+        return _contacts.TouchReport(count, count > 0, dist, normal, force)
 
     def episode_returns(self):
         return self.ep_return

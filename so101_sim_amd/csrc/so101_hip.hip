@@ -876,18 +876,8 @@ int so101_debug_forward(so101_sim* s, float* out, void* stream) {
 // ---- contact sensing (csrc/so101_contacts.hpp)
 int so101_contacts(so101_sim* s, const int32_t* env_index, int n, int forces, const so101_geom_pair* pairs, int npair, const so101_contact_out* out, void* stream) {
   if (!s) return SO101_ERR_ARG;
-  const char* bad = nullptr;
   const so101_contact_out* o = out;
-  if (!o) bad = "NULL out";
-  else if (!o->count && !o->flags && !o->geom && !o->dist && !o->pos && !o->frame && !o->force && !o->pair_count && !o->pair_dist && !o->pair_normal && !o->pair_force)
-    bad = "no output (every pointer of out is NULL)";
-  else if (n < 1 || n > (1 << 26)) bad = "n must be 1 .. 2^26";
-  else if (!env_index && n > s->n_envs) bad = "n exceeds the envs of the handle";
-  else if (npair < 0 || npair > SO101_TOUCH_MAX_PAIRS) bad = "npair must be 0 .. 16";
-  else if (npair > 0 && !pairs) bad = "NULL pairs with npair > 0";
-  else if (npair == 0 && (o->pair_count || o->pair_dist || o->pair_normal || o->pair_force)) bad = "a pair output with npair == 0";
-  else if (!forces && (o->force || o->pair_normal || o->pair_force)) bad = "force, pair_normal and pair_force need forces != 0";
-  if (bad) { s->err = std::string("so101_contacts: ") + bad; return SO101_ERR_ARG; }
+  if (int rc = check_contact_arguments(s, "so101_contacts", o, env_index != nullptr, n, s->n_envs, forces, pairs != nullptr, npair)) return rc;          // (so101_host.hpp)
   const int ngeom = s->hm.ngeom;
   if (ngeom > 128) { s->err = "so101_contacts: the model has more than 128 geoms (a group mask has 128 bits)"; return SO101_ERR_STATE; }
   TouchPairs T{};
@@ -895,13 +885,7 @@ int so101_contacts(so101_sim* s, const int32_t* env_index, int n, int forces, co
   for (int p = 0; p < npair; p++) {
     for (int side = 0; side < 2; side++) {
       const uint32_t* w = side ? pairs[p].b : pairs[p].a;
-      bool any = false;
-      for (int g = 0; g < 128; g++) {
-        if (!((w[g >> 5] >> (g & 31)) & 1u)) continue;
-        any = true;
-        if (g >= ngeom) { s->err = "so101_contacts: pair " + std::to_string(p) + ", group " + (side ? "b" : "a") + ": bit " + std::to_string(g) + " is at or beyond ngeom = " + std::to_string(ngeom); return SO101_ERR_ARG; }
-      }
-      if (!any) { s->err = "so101_contacts: pair " + std::to_string(p) + ", group " + (side ? "b" : "a") + " is empty"; return SO101_ERR_ARG; }
+      if (int rc = check_contact_group(s, "so101_contacts", w, 4, p, side, ngeom)) return rc;
       memcpy(side ? T.b[p] : T.a[p], w, sizeof T.a[p]);
     }
   }

@@ -372,3 +372,38 @@ int ik_settings(HostHandle* s, const char* api, const Cfg* cfg, int nio, unsigne
   for (int k = 0; k < nio; k++) { C.q_lo[k] = cfg->q_lo[k]; C.q_hi[k] = cfg->q_hi[k]; }
   return SO101_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------- contact sensing
+// What so101_contacts and so101_tree_contacts check before they launch (so101_contacts.hpp, so101_tree_contacts.hpp), in the order their header
+// comment lists it.  Each returns SO101_OK or SO101_ERR_ARG with "<api>: <what>" in s->err.
+
+// the outputs, the count and the pair arguments (the groups themselves: check_contact_group)
+inline int check_contact_arguments(HostHandle* s, const char* api, const so101_contact_out* o, bool has_index, int n, int n_envs, int forces, bool has_pairs, int npair) {
+  const char* bad = nullptr;
+  if (!o) bad = "NULL out";
+  else if (!o->count && !o->flags && !o->geom && !o->dist && !o->pos && !o->frame && !o->force && !o->pair_count && !o->pair_dist && !o->pair_normal && !o->pair_force)
+    bad = "no output (every pointer of out is NULL)";
+  else if (n < 1 || n > (1 << 26)) bad = "n must be 1 .. 2^26";
+  else if (!has_index && n > n_envs) bad = "n exceeds the envs of the handle";
+  else if (npair < 0 || npair > SO101_TOUCH_MAX_PAIRS) bad = "npair must be 0 .. 16";
+  else if (npair > 0 && !has_pairs) bad = "NULL pairs with npair > 0";
+  else if (npair == 0 && (o->pair_count || o->pair_dist || o->pair_normal || o->pair_force)) bad = "a pair output with npair == 0";
+  else if (!forces && (o->force || o->pair_normal || o->pair_force)) bad = "force, pair_normal and pair_force need forces != 0";
+  if (bad) { s->err = std::string(api) + ": " + bad; return SO101_ERR_ARG; }
+  return SO101_OK;
+}
+
+// one group of pair p (side 0: a, 1: b), `nword` 32-bit words: not empty, no bit at or beyond ngeom
+inline int check_contact_group(HostHandle* s, const char* api, const uint32_t* w, int nword, int p, int side, int ngeom) {
+  bool any = false;
+  for (int g = 0; g < 32 * nword; g++) {
+    if (!((w[g >> 5] >> (g & 31)) & 1u)) continue;
+    any = true;
+    if (g >= ngeom) {
+      s->err = std::string(api) + ": pair " + std::to_string(p) + ", group " + (side ? "b" : "a") + ": bit " + std::to_string(g) + " is at or beyond ngeom = " + std::to_string(ngeom);
+      return SO101_ERR_ARG;
+    }
+  }
+  if (!any) { s->err = std::string(api) + ": pair " + std::to_string(p) + ", group " + (side ? "b" : "a") + " is empty"; return SO101_ERR_ARG; }
+  return SO101_OK;
+}

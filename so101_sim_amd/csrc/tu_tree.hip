@@ -23,6 +23,7 @@
 #endif
 
 #include "so101_tree_kernels.hpp"
+#include "so101_tree_contacts.hpp"
 #include "so101_tree_host.hpp"
 
 namespace TREE_NS {
@@ -344,6 +345,35 @@ int TAPI(tool_ik)(TreeHandle* s, const so101_tree_tool* tool, const so101_tree_i
   GUARD_DEVICE(s);
   so101::launch_tool_ik(n, (hipStream_t)stream, T, C, target_pos, target_mat, q_init, (const float*)s->buf.qpos, s->n_envs, (const int*)env_index, q_out, residual, (int*)info);
   return hip_ok(s, hipGetLastError(), "k_tool_ik") ? SO101_OK : SO101_ERR_HIP;
+}
+
+// ---- contact sensing (so101_tree_contacts.hpp)
+int TAPI(contacts)(TreeHandle* s, const int32_t* env_index, int n, int forces, const so101_tree_geom_pair* pairs, int npair, const so101_contact_out* out, void* stream) {
+  if (!s) return SO101_ERR_ARG;
+  const so101_contact_out* o = out;
+  if (int rc = check_contact_arguments(s, "so101_tree_contacts", o, env_index != nullptr, n, s->n_envs, forces, pairs != nullptr, npair)) return rc;          // (so101_host.hpp)
+  TreeTouchPairs T{};
+  T.npair = npair;
+  for (int p = 0; p < npair; p++) {
+    for (int side = 0; side < 2; side++) {
+      const uint32_t* w = side ? pairs[p].b : pairs[p].a;
+      if (int rc = check_contact_group(s, "so101_tree_contacts", w, 8, p, side, s->hm.ngeom)) return rc;
+      memcpy(side ? T.b[p] : T.a[p], w, sizeof T.a[p]);
+    }
+  }
+  if (!s->bound) { s->err = "so101_tree_contacts: state buffers not bound (call so101_tree_bind_state)"; return SO101_ERR_STATE; }
+  GUARD_DEVICE(s);
+  ContactOut O{(int*)o->count, (int*)o->flags, (int*)o->geom, o->dist, o->pos, o->frame, o->force, (int*)o->pair_count, o->pair_dist, o->pair_normal, o->pair_force};
+  // with forces entry i works in scratch slice i mod n_envs (env_index may repeat an env): at most n_envs entries per launch, the launches in
+  // stream order; without forces the scratch is not touched and one launch serves any n
+  const int chunk = forces ? s->n_envs : n;
+  for (int i0 = 0; i0 < n; i0 += chunk) {
+    const int cnt = n - i0 < chunk ? n - i0 : chunk;
+    hipLaunchKernelGGL(k_tree_contacts, dim3((unsigned int)cnt), dim3(64), 0, (hipStream_t)stream, s->dm, s->dg, s->buf, s->n_envs, s->iterations, s->tolerance, (const int*)env_index, i0,
+                       (int)(forces != 0), T, O);
+    if (!hip_ok(s, hipGetLastError(), "k_tree_contacts")) return SO101_ERR_HIP;
+  }
+  return SO101_OK;
 }
 
 int TAPI(get_diag)(TreeHandle* s, int* out /* [n_envs][8] device or host-visible memory */, void* stream) {

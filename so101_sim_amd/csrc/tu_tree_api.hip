@@ -1,5 +1,5 @@
 // Public entry points of the general-tree engine (include/so101.h, so101_tree_*): a handle names one of the two builds of
-// csrc/so101_tree.hpp (with its kernels, so101_tree_kernels.hpp, and host code, so101_tree_host.hpp) - 32 dofs / 128 geoms / 64 contacts (tu_tree.hip: the ALOHA hand-over scenes) or 64 dofs / 256 geoms / 128 contacts
+// csrc/so101_tree.hpp (with its kernels, so101_tree_kernels.hpp, and host code, so101_tree_host.hpp) - 32 dofs / 128 geoms / 64 contacts (tu_tree.hip: the ALOHA hand-over scenes) or 64 dofs / 256 geoms / 160 contacts
 // (tu_tree64.hip: the Dining scenes) - chosen by so101_tree_create from the model's dimensions; every other call forwards.
 #include <cstddef>
 #include <cstdint>
@@ -34,7 +34,8 @@
   int so101_tree##V##_ik_default_config(void*, int, so101_tree_ik_config*);                                                                    \
   int so101_tree##V##_tool_pose(void*, const so101_tree_tool*, const float*, const int32_t*, int, float*, float*, float*, void*);              \
   int so101_tree##V##_tool_ik(void*, const so101_tree_tool*, const so101_tree_ik_config*, const float*, const float*, const float*, const int32_t*, int, float*, float*, \
-                              int32_t*, void*);
+                              int32_t*, void*);                                                                                                \
+  int so101_tree##V##_contacts(void*, const int32_t*, int, int, const so101_tree_geom_pair*, int, const so101_contact_out*, void*);
 
 // (the builds define these with their own handle type in place of void*: same C symbol, same calling convention)
 extern "C" {
@@ -118,6 +119,9 @@ int so101_tree_tool_pose(so101_tree* s, const so101_tree_tool* tool, const float
 int so101_tree_tool_ik(so101_tree* s, const so101_tree_tool* tool, const so101_tree_ik_config* cfg, const float* target_pos, const float* target_mat, const float* q_init,
                        const int32_t* env_index, int n, float* q_out, float* residual, int32_t* info, void* stream) {
   return s ? FWD(tool_ik, tool, cfg, target_pos, target_mat, q_init, env_index, n, q_out, residual, info, stream) : SO101_ERR_ARG;
+}
+int so101_tree_contacts(so101_tree* s, const int32_t* env_index, int n, int forces, const so101_tree_geom_pair* pairs, int npair, const so101_contact_out* out, void* stream) {
+  return s ? FWD(contacts, env_index, n, forces, pairs, npair, out, stream) : SO101_ERR_ARG;
 }
 
 }  // extern "C"

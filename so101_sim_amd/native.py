@@ -36,7 +36,7 @@ EXPORTS = (
     "so101_tree_create", "so101_tree_destroy", "so101_tree_dims", "so101_tree_last_plan", "so101_tree_bind_state", "so101_tree_configure", "so101_tree_physics",
     "so101_tree_debug_forward", "so101_tree_get_diag", "so101_tree_last_error", "so101_tree_obs_dim", "so101_tree_bind_env",
     "so101_tree_configure_env", "so101_tree_bind_physics_state", "so101_tree_reset", "so101_tree_step", "so101_tree_set_hull_planes", "so101_tree_render", "so101_tree_begin_episode", "so101_tree_settle", "so101_tree_compute_settled", "so101_tree_set_settled_store",
-    "so101_tree_tool_chain", "so101_tree_ik_default_config", "so101_tree_tool_pose", "so101_tree_tool_ik",
+    "so101_tree_tool_chain", "so101_tree_ik_default_config", "so101_tree_tool_pose", "so101_tree_tool_ik", "so101_tree_contacts",
 )
 
 
@@ -104,6 +104,20 @@ class ContactOut(C.Structure):
 def geom_pair_array(pairs):
     """((a words[4], b words[4]), ...) as the so101_geom_pair array of so101_contacts"""
     arr = (GeomPair * max(len(pairs), 1))()
+    for k, (a, b) in enumerate(pairs):
+        arr[k].a[:] = [int(x) & 0xFFFFFFFF for x in a]
+        arr[k].b[:] = [int(x) & 0xFFFFFFFF for x in b]
+    return arr
+
+
+class TreeGeomPair(C.Structure):
+    """so101_tree_geom_pair of include/so101.h: two 256-bit geom masks"""
+    _fields_ = [("a", C.c_uint32 * 8), ("b", C.c_uint32 * 8)]
+
+
+def tree_geom_pair_array(pairs):
+    """((a words[8], b words[8]), ...) as the so101_tree_geom_pair array of so101_tree_contacts"""
+    arr = (TreeGeomPair * max(len(pairs), 1))()
     for k, (a, b) in enumerate(pairs):
         arr[k].a[:] = [int(x) & 0xFFFFFFFF for x in a]
         arr[k].b[:] = [int(x) & 0xFFFFFFFF for x in b]
@@ -382,6 +396,7 @@ class TreeSim:
         L.so101_tree_ik_default_config.argtypes = [vp, C.c_int, C.POINTER(TreeIkConfig)]
         L.so101_tree_tool_pose.argtypes = [vp, C.POINTER(ToolSpec), vp, vp, C.c_int, vp, vp, vp, vp]
         L.so101_tree_tool_ik.argtypes = [vp, C.POINTER(ToolSpec), C.POINTER(TreeIkConfig), vp, vp, vp, vp, C.c_int, vp, vp, vp, vp]
+        L.so101_tree_contacts.argtypes = [vp, vp, C.c_int, C.c_int, C.POINTER(TreeGeomPair), C.c_int, C.POINTER(ContactOut), vp]
         self.n_envs = int(n_envs)
         h = C.c_void_p()
         rc = L.so101_tree_create(blob_f32, len(blob_f32), self.n_envs, int(device), C.byref(h))
@@ -516,3 +531,9 @@ class TreeSim:
         """so101_tree_tool_ik; cfg from ik_config(); the arrays are raw device addresses or None"""
         self._check(self.L.so101_tree_tool_ik(self.h, C.byref(tool_spec(tool)), C.byref(cfg), target_pos, target_mat, q_init, env_index, int(n),
                                               q_out, residual, info, stream), "so101_tree_tool_ik")
+
+    def contacts(self, env_index, n: int, forces: bool, pairs, out: ContactOut, stream=0):
+        """so101_tree_contacts; pairs: sequence of (a words[8], b words[8]) geom masks; env_index and the fields of `out`: raw device addresses or
+        None.  The per-contact fields of `out` have max_contacts slots per entry."""
+        arr = tree_geom_pair_array(pairs) if pairs else None
+        self._check(self.L.so101_tree_contacts(self.h, env_index, int(n), int(bool(forces)), arr, len(pairs) if pairs else 0, C.byref(out), stream), "so101_tree_contacts")
