@@ -524,7 +524,7 @@ int so101_tree_tool_pose(so101_tree* sim, const so101_tree_tool* tool, const flo
  * so101_tool_ik on the configuration (q_lo <= q_hi over the chain's columns), and free_mask bits at or above ncol. */
 int so101_tree_tool_ik(so101_tree* sim, const so101_tree_tool* tool, const so101_tree_ik_config* cfg, const float* target_pos, const float* target_mat,
                        const float* q_init, const int32_t* env_index, int n, float* q_out, float* residual, int32_t* info, void* hip_stream);
-/* ---- contact sensing of this engine (csrc/so101_tree_contacts.hpp): so101_contacts above on a tree handle, for both builds - the same semantics
+/* ---- contact sensing of this engine (k_tree_contacts of csrc/so101_tree_kernels.hpp): so101_contacts above on a tree handle, for both builds - the same semantics
  * and conventions with this engine's stages and capacity.  The pass is so101_tree_debug_forward's cut down to the report: kinematics and collision for
  * the geometry; with forces != 0 also the mass matrix, the bias forces, the smooth dynamics, the constraint rows and the Newton solve with the handle's
  * iterations and tolerance (so101_tree_configure) - with forces == 0 none of that runs.  Its numbers are so101_tree_debug_forward's bit for bit.

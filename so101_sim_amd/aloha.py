@@ -30,6 +30,7 @@ from . import native
 from ._dmenv import Array, BoundedArray, TimeStep
 from .model import blob as blobfmt
 from .model import scenes
+from . import contacts as _contacts
 from .tool_control import ToolControl
 
 DEFAULT_CONTROL_TIMESTEP = 0.02
@@ -135,7 +136,7 @@ def aloha_action_spec(ctrlrange: np.ndarray, waist_joint_limit: float = np.pi / 
     return BoundedArray((14,), np.float32, lo, hi)
 
 
-class AlohaEnvironment(ToolControl):
+class AlohaEnvironment(ToolControl, _contacts.ContactSensing):
     def __init__(self, task: HandOverTask, n_envs: int = 1, time_limit: float = float("inf"), random_state=None, device=None,
                  env_id_base: int = 0, solver_iterations: int = 0, solver_tolerance: float = -1.0, settle_max_substeps: int = 1000,
                  physics_state: bool | None = None, seed_compatible: bool = True, narrowphase: str = "epa", prefetch_resets: bool = True, pipeline: bool = True):
@@ -530,9 +531,11 @@ class AlohaEnvironment(ToolControl):
                 action[:, a] = self._f32(g)
         return action
 
-    # ------------------------------------------------------------------ contact sensing (contacts.py)
+    # ------------------------------------------------------------------ contact sensing (contacts.py: ContactSensing)
+    _geom_limit = _contacts.TREE_MAX_GEOMS
+    _contact_capacity = property(lambda self: self.sim.max_contacts)          # (64 in the hand-over scenes, 160 in Dining)
+
     def _geom_groups(self):
-        from . import contacts as _contacts
         if getattr(self, "_groups", None) is None:
             self._groups = _contacts.aloha_groups(self.meta, blobfmt.unpack(self.task.load_blob("f32")[0]))
         return self._groups
@@ -542,8 +545,7 @@ class AlohaEnvironment(ToolControl):
         "left_gripper", "right_gripper", "grippers", "object", "container", "props"), a geom name, an fnmatch pattern over the geom names, an
         iterable of geom ids or a GeomGroup.  ALOHA geom names are not unique (`vx300s_8_custom_finger_left` occurs once per arm): a geom
         name or a pattern resolves to ALL geoms that match."""
-        from . import contacts as _contacts
-        return _contacts.resolve(spec, self._geom_groups(), self.meta, limit=_contacts.TREE_MAX_GEOMS)
+        return self._geom_group(spec)
 
     def contacts(self, env_ids=None, forces: bool = False):
         """The contact lists of the envs `env_ids` (None = all) at their current state, on the GPU (so101_tree_contacts): a
@@ -555,16 +557,7 @@ class AlohaEnvironment(ToolControl):
         solve, warmstart read and left alone), not the impulses of the last substep; without forces only kinematics and collision run.
         There is no `physics` facade on this environment: `contacts.records(report, entry)` gives the list of `physics.data.contact`-like
         records of one entry."""
-        from . import contacts as _contacts
-        torch = self.torch
-        idx, n = self._env_index(env_ids)
-        C = self.sim.max_contacts
-        e = lambda *s, dt=torch.float32: torch.empty(*s, dtype=dt, device=self.device)
-        rep = _contacts.ContactReport(e(n, dt=torch.int32), e(n, dt=torch.int32), e(n, C, 2, dt=torch.int32), e(n, C), e(n, C, 3), e(n, C, 3, 3),
-                                      e(n, C, 6) if forces else None)
-        out = native.ContactOut(**{k: (t.data_ptr() if t is not None else None) for k, t in rep._asdict().items()})
-        self.sim.contacts(idx.data_ptr() if idx is not None else None, n, forces, None, out, self._stream())
-        return rep
+        return self._contacts(env_ids, forces)
 
     def touch(self, pairs, env_ids=None, forces: bool = False):
         """Who touches whom: `pairs` is a sequence of at most 16 (a, b), each side anything geom_group() takes.  Per env of `env_ids` (None = all)
@@ -573,21 +566,7 @@ class AlohaEnvironment(ToolControl):
         normal_force [n, npair] (sum of the normal forces) and force [n, npair, 3] (the net world-frame force ON group a), else None.
         `("right_gripper", "object")`, `("left_gripper", "object")` and `("object", "container")` are the questions of the contact-sequence
         reward (hand_over.py:286-338), the last one that of the Dining `contact` reward."""
-        from . import contacts as _contacts
-        torch = self.torch
-        pairs = list(pairs)
-        if not 1 <= len(pairs) <= _contacts.MAX_PAIRS:
-            raise ValueError(f"touch takes 1 .. {_contacts.MAX_PAIRS} pairs, got {len(pairs)}")
-        masks = [(self.geom_group(a).mask(8), self.geom_group(b).mask(8)) for a, b in pairs]
-        idx, n = self._env_index(env_ids)
-        P = len(masks)
-        e = lambda *s, dt=torch.float32: torch.empty(*s, dtype=dt, device=self.device)
-        count, dist = e(n, P, dt=torch.int32), e(n, P)
-        normal, force = (e(n, P), e(n, P, 3)) if forces else (None, None)
-        out = native.ContactOut(pair_count=count.data_ptr(), pair_dist=dist.data_ptr(), pair_normal=normal.data_ptr() if forces else None,
-                                pair_force=force.data_ptr() if forces else None)
-        self.sim.contacts(idx.data_ptr() if idx is not None else None, n, forces, masks, out, self._stream())
-        return _contacts.TouchReport(count, count > 0, dist, normal, force)
+        return self._touch(pairs, env_ids, forces)
 
     def episode_returns(self):
         return self.ep_return

@@ -199,3 +199,45 @@ def records(report: ContactReport, entry: int = 0) -> list:
     pos = report.pos[entry, :n].cpu().numpy().astype(np.float64)
     frame = report.frame[entry, :n].cpu().numpy().astype(np.float64).reshape(n, 9)
     return [ContactRecord(geom[k, 0], geom[k, 1], dist[k], pos[k], frame[k]) for k in range(n)]
+
+
+class ContactSensing:
+    """Contact sensing shared by the batched environments (`BatchedEnvironment` of env.py on the SO100 engine, `AlohaEnvironment` of aloha.py
+    on the general-tree engine), on the pattern of tool_control.ToolControl: output allocation and argument handling of `contacts` and `touch`.
+
+    An environment supplies `_geom_groups()` (the scene's groups: so100_groups / aloha_groups), `_geom_limit` (the id limit of its group
+    masks, MAX_GEOMS or TREE_MAX_GEOMS) and `_contact_capacity` (contacts per entry), and keeps its own public `geom_group` / `contacts` /
+    `touch` with their documentation; `self.sim` has contacts (native.Sim, native.TreeSim), `_env_index` comes from ToolControl."""
+
+    def _geom_group(self, spec) -> GeomGroup:
+        return resolve(spec, self._geom_groups(), self.meta, limit=self._geom_limit)
+
+    def _contacts(self, env_ids, forces) -> ContactReport:
+        from . import native
+        torch = self.torch
+        idx, n = self._env_index(env_ids)
+        C = self._contact_capacity
+        e = lambda *s, dt=torch.float32: torch.empty(*s, dtype=dt, device=self.device)
+        rep = ContactReport(e(n, dt=torch.int32), e(n, dt=torch.int32), e(n, C, 2, dt=torch.int32), e(n, C), e(n, C, 3), e(n, C, 3, 3),
+                            e(n, C, 6) if forces else None)
+        out = native.ContactOut(**{k: (t.data_ptr() if t is not None else None) for k, t in rep._asdict().items()})
+        self.sim.contacts(idx.data_ptr() if idx is not None else None, n, forces, None, out, self._stream())
+        return rep
+
+    def _touch(self, pairs, env_ids, forces) -> TouchReport:
+        from . import native
+        torch = self.torch
+        pairs = list(pairs)
+        if not 1 <= len(pairs) <= MAX_PAIRS:
+            raise ValueError(f"touch takes 1 .. {MAX_PAIRS} pairs, got {len(pairs)}")
+        words = self._geom_limit // 32
+        masks = [(self.geom_group(a).mask(words), self.geom_group(b).mask(words)) for a, b in pairs]
+        idx, n = self._env_index(env_ids)
+        P = len(masks)
+        e = lambda *s, dt=torch.float32: torch.empty(*s, dtype=dt, device=self.device)
+        count, dist = e(n, P, dt=torch.int32), e(n, P)
+        normal, force = (e(n, P), e(n, P, 3)) if forces else (None, None)
+        out = native.ContactOut(pair_count=count.data_ptr(), pair_dist=dist.data_ptr(), pair_normal=normal.data_ptr() if forces else None,
+                                pair_force=force.data_ptr() if forces else None)
+        self.sim.contacts(idx.data_ptr() if idx is not None else None, n, forces, masks, out, self._stream())
+        return TouchReport(count, count > 0, dist, normal, force)

@@ -873,26 +873,18 @@ int so101_debug_forward(so101_sim* s, float* out, void* stream) {
   return SO101_OK;
 }
 
-// ---- contact sensing (csrc/so101_contacts.hpp)
+// ---- contact sensing (csrc/so101_contacts.hpp; the checks and the packing: so101_host.hpp)
 int so101_contacts(so101_sim* s, const int32_t* env_index, int n, int forces, const so101_geom_pair* pairs, int npair, const so101_contact_out* out, void* stream) {
   if (!s) return SO101_ERR_ARG;
   const so101_contact_out* o = out;
   if (int rc = check_contact_arguments(s, "so101_contacts", o, env_index != nullptr, n, s->n_envs, forces, pairs != nullptr, npair)) return rc;          // (so101_host.hpp)
   const int ngeom = s->hm.ngeom;
   if (ngeom > 128) { s->err = "so101_contacts: the model has more than 128 geoms (a group mask has 128 bits)"; return SO101_ERR_STATE; }
-  TouchPairs T{};
-  T.npair = npair;
-  for (int p = 0; p < npair; p++) {
-    for (int side = 0; side < 2; side++) {
-      const uint32_t* w = side ? pairs[p].b : pairs[p].a;
-      if (int rc = check_contact_group(s, "so101_contacts", w, 4, p, side, ngeom)) return rc;
-      memcpy(side ? T.b[p] : T.a[p], w, sizeof T.a[p]);
-    }
-  }
+  TouchPairsT<4> T{};
+  if (int rc = pack_touch_pairs(s, "so101_contacts", pairs, npair, ngeom, T)) return rc;
   if (!s->bound) { s->err = "so101_contacts: state buffers not bound (call so101_bind_state)"; return SO101_ERR_STATE; }
   GUARD_DEVICE(s);
-  ContactOut O{(int*)o->count, (int*)o->flags, (int*)o->geom, o->dist, o->pos, o->frame, o->force, (int*)o->pair_count, o->pair_dist, o->pair_normal, o->pair_force};
-  so101::launch_contacts(s->cfg.solver, n, (hipStream_t)stream, s->dm, make_params(s), s->buf, (const int*)env_index, forces != 0, T, O);
+  so101::launch_contacts(s->cfg.solver, n, (hipStream_t)stream, s->dm, make_params(s), s->buf, (const int*)env_index, forces != 0, T, contact_out_of(o));
   LAUNCH_CHECK(s, "k_contacts");
   return SO101_OK;
 }

@@ -8,6 +8,7 @@
 #include "../../include/so101.h"
 #include "so101_tables.hpp"
 #include "so101_tool_chain.hpp"
+#include "so101_contact_report.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -374,8 +375,9 @@ int ik_settings(HostHandle* s, const char* api, const Cfg* cfg, int nio, unsigne
 }
 
 // ---------------------------------------------------------------------------------------------------- contact sensing
-// What so101_contacts and so101_tree_contacts check before they launch (so101_contacts.hpp, so101_tree_contacts.hpp), in the order their header
-// comment lists it.  Each returns SO101_OK or SO101_ERR_ARG with "<api>: <what>" in s->err.
+// What so101_contacts and so101_tree_contacts check before they launch (k_contacts of so101_contacts.hpp, k_tree_contacts of so101_tree_kernels.hpp),
+// in the order their header comment lists it, and how they pack the kernel arguments of the shared report (so101_contact_report.hpp).  Each check
+// returns SO101_OK or SO101_ERR_ARG with "<api>: <what>" in s->err.
 
 // the outputs, the count and the pair arguments (the groups themselves: check_contact_group)
 inline int check_contact_arguments(HostHandle* s, const char* api, const so101_contact_out* o, bool has_index, int n, int n_envs, int forces, bool has_pairs, int npair) {
@@ -406,4 +408,22 @@ inline int check_contact_group(HostHandle* s, const char* api, const uint32_t* w
   }
   if (!any) { s->err = std::string(api) + ": pair " + std::to_string(p) + ", group " + (side ? "b" : "a") + " is empty"; return SO101_ERR_ARG; }
   return SO101_OK;
+}
+
+// the npair pairs of a call, checked group by group (pair 0 side a, pair 0 side b, pair 1 ...) and packed into the kernel argument
+template <int NW, class Pair>
+int pack_touch_pairs(HostHandle* s, const char* api, const Pair* pairs, int npair, int ngeom, TouchPairsT<NW>& T) {
+  T.npair = npair;
+  for (int p = 0; p < npair; p++) {
+    for (int side = 0; side < 2; side++) {
+      const uint32_t* w = side ? pairs[p].b : pairs[p].a;
+      if (int rc = check_contact_group(s, api, w, NW, p, side, ngeom)) return rc;
+      memcpy(side ? T.b[p] : T.a[p], w, sizeof T.a[p]);
+    }
+  }
+  return SO101_OK;
+}
+
+inline ContactOut contact_out_of(const so101_contact_out* o) {
+  return ContactOut{(int*)o->count, (int*)o->flags, (int*)o->geom, o->dist, o->pos, o->frame, o->force, (int*)o->pair_count, o->pair_dist, o->pair_normal, o->pair_force};
 }

@@ -7,6 +7,7 @@
 
 template <int NC> struct ToolChain;          // so101_tool_chain.hpp
 template <int NC> struct IkSettings;
+template <int NW> struct TouchPairsT;        // so101_contact_report.hpp
 
 namespace so101 {
 
@@ -28,7 +29,7 @@ void launch_physics(int solver, int n_envs, hipStream_t st, const DevModel* m, c
 void launch_debug_forward(int solver, int n_envs, hipStream_t st, const DevModel* m, const StepParams& P, const DevBuffers& B, float* out);
 // contact sensing (so101_contacts.hpp): one wavefront per reported env, n of them; env_index NULL = envs 0 .. n - 1
 void launch_contacts(int solver, int n, hipStream_t st, const DevModel* m, const StepParams& P, const DevBuffers& B, const int* env_index, int forces,
-                     const TouchPairs& T, const ContactOut& O);
+                     const TouchPairsT<4>& T, const ContactOut& O);
 void launch_begin(int n_envs, hipStream_t st, const DevModel* m, const StepParams& P, const DevBuffers& B, unsigned char* need_reset);
 void launch_reward(int n_envs, hipStream_t st, const DevModel* m, const StepParams& P, const DevBuffers& B, float* reward);
 
@@ -77,6 +78,6 @@ void launch_step_pgs(int n_envs, hipStream_t st, const DevModel* m, const StepPa
 void launch_physics_pgs(int n_envs, hipStream_t st, const DevModel* m, const StepParams& P, const DevBuffers& B, int nsub, int freeze, int* diag);
 void launch_debug_forward_pgs(int n_envs, hipStream_t st, const DevModel* m, const StepParams& P, const DevBuffers& B, float* out);
 void launch_contacts_pgs(int n, hipStream_t st, const DevModel* m, const StepParams& P, const DevBuffers& B, const int* env_index, int forces,
-                         const TouchPairs& T, const ContactOut& O);
+                         const TouchPairsT<4>& T, const ContactOut& O);
 
 }  // namespace so101

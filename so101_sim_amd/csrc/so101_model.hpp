@@ -294,12 +294,8 @@ struct ChainParams { const DevModel* m; StepParams P; DevBuffers B; EventBuffers
 struct RenderCam { int body; float pos[3], mat[9], scale; };      // body: -1 world, else as geom_dyn numbers the bodies (SO100: 0 .. NDYN - 1, tree: the body id); scale = 2 tan(fovy / 2) / H
 struct RenderCams { RenderCam cam[RENDER_MAXCAM]; };
 
-// ---- contact sensing (so101_contacts.hpp): the geom-group pairs of one so101_contacts call (a kernel argument) and its outputs
+// ---- contact sensing: the outputs of one so101_contacts / so101_tree_contacts call (its geom-group pairs: TouchPairsT of so101_contact_report.hpp)
 #define TOUCH_MAX_PAIRS 16        // SO101_TOUCH_MAX_PAIRS of include/so101.h
-struct TouchPairs {               // bit (g & 31) of word g >> 5: geom g belongs to the group
-  int npair;
-  unsigned int a[TOUCH_MAX_PAIRS][4], b[TOUCH_MAX_PAIRS][4];
-};
 struct ContactOut {               // so101_contact_out: device pointers, any may be NULL
   int *count, *flags, *geom;
   float *dist, *pos, *frame, *force;

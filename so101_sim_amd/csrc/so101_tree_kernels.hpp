@@ -2,6 +2,7 @@
 // once per build of the engine (TREE_VARIANT): no include guard, every macro is undefined before it is defined.
 // so101_tree_debug_forward layout (floats per env; dims[7..14] of so101_tree_dims report it): counts, bias, qacc_smooth, qacc [TV each],
 // body positions [TB][3], mass matrix [TV][TV], contacts [TCON][10] (pos3 normal3 dist geom1 geom2 dim), normal forces [TCON]
+#include "so101_contact_report.hpp"      // (guarded: the report tail of k_tree_contacts is one template for both builds)
 #undef TDBG_COUNTS
 #undef TDBG_BIAS
 #undef TDBG_QSM
@@ -444,5 +445,66 @@ __global__ void __launch_bounds__(64) k_tree_render_frames(const TreeModel* tm, 
       f[12] = cams.cam[k].scale;
     }
   }
+}
+
+// ---- contact sensing (so101_tree_contacts of include/so101.h): the contact list of an env's CURRENT bound state and its reduction over pairs of
+// geom groups, one wavefront per reported entry.  The pass is tree::forward() cut down to the report, its stages in forward()'s order - which is
+// what makes the numbers bit-identical to k_tree_forward's dump: load_state, kinematics; with `forces` crba, rne_bias, smooth; collision; with
+// `forces` make_constraints and solve_newton with the handle's iterations and tolerance.  `forces` is a kernel argument: the branch is
+// wave-uniform, and without it none of the dynamics runs.  Nothing is stored back - no store_state, no store_diag, the warmstart is read and left
+// alone.  Everything after the pass is contact_report() of so101_contact_report.hpp, shared with the SO100 engine.
+//
+// Where the numbers come from (TreeContactView):
+//   * TCon::frame is the FULL frame: write_contact() puts the normal (geom1 -> geom2) into row 0 and make_frame() completes rows 1 and 2.
+//   * count and the per-contact geometry are those after collision(), read before make_constraints() runs: make_constraints() lowers L.ncon when
+//     the rows of the last contacts do not fit TROW (flag 4).  Geometry with and without forces is therefore the same, bit for bit; the
+//     contacts that got no rows (k >= nkeep) report zero force and add nothing to the sums.
+//   * force[j] = G.ef[c.row + j] for j < c.dim, zero beyond - read through the TreeScratch the solve used (use_row_storage() may have moved the
+//     rows into LDS) - and only when the pass has rows at all (nrow > 0, as k_tree_forward's TDBG_FORCE): without rows solve_newton() returns
+//     before anything writes ef.
+//   * L.flags, started at 0, is the flag word of THIS pass: 1 candidate overflow, 2 contact overflow (collision() ends the list at the first
+//     pair that does not fit), with forces 4 (contacts dropped for rows).
+//
+// Scratch: make_constraints() and solve_newton() work in a per-env slice of B.scratch.  env_index may name an env more than once, and two
+// wavefronts on one slice would race: entry i works in slice i mod n_envs, and the host enqueues at most n_envs entries per launch
+// (tu_tree.hip).  No kernel of this engine reads scratch it did not write in the same launch, so whose slice it is does not matter.
+struct TreeContactView {
+  static constexpr int DIST = (int)(offsetof(TCon, dist) / 4), POS = (int)(offsetof(TCon, pos) / 4), FRAME = (int)(offsetof(TCon, frame) / 4);
+  const TreeLDS& L;
+  const TreeScratch& G;
+  int count, flags, nkeep;
+  bool solved;
+  DEV int g1(int k) const { return L.con[k].g1; }
+  DEV int g2(int k) const { return L.con[k].g2; }
+  DEV const float* words(int k) const { return (const float*)&L.con[k]; }
+  DEV float force(int k, int j) const { return solved && k < nkeep && j < L.con[k].dim ? G.ef[L.con[k].row + j] : 0.f; }
+};
+
+// entries i0 .. i0 + gridDim.x - 1 of the call; with forces at most N of them per launch (the scratch slices)
+__global__ void __launch_bounds__(64) k_tree_contacts(const TreeModel* tm, const DevModel* gm, TreeBuffers B, int N, int iterations, float tolerance, const int* env_index, int i0,
+                                                      int forces, TouchPairsT<8> T, ContactOut O) {
+  BLOCK_SHARED(TreeLDS, L);
+  const size_t i = (size_t)i0 + blockIdx.x;
+  const int e = env_index ? wave_uniform_i(env_index[i]) : (int)i;
+  if (e < 0 || e >= N) { contacts_outside<TCON>(i, T.npair, O); return; }
+  if (wave_lane() == 0) L.flags = 0;
+  tree::load_state(tm, L, B, e, N);
+  tree::kinematics(tm, L);
+  if (forces) {                     // (wave-uniform: a kernel argument)
+    tree::crba(tm, L);
+    tree::rne_bias(tm, L);
+    tree::smooth(tm, L);
+  }
+  tree::collision(tm, gm, L);
+  const int ncon = L.ncon;          // the list of collision(): make_constraints() may shorten it
+  int nkeep = ncon, nrow = 0;
+  TreeScratch G = tree::scratch_of(B, (int)(i % (size_t)N));
+  if (forces) {
+    tree::make_constraints(tm, L, G);
+    tree::solve_newton(tm, L, G, iterations, tolerance);
+    nkeep = L.ncon; nrow = L.nrow;
+  }
+  wave_sync();
+  contact_report<TCON>(i, TreeContactView{L, G, ncon, L.flags, nkeep, forces && nrow > 0}, forces != 0, T, O);
 }
 }  // namespace TREE_NS

@@ -41,7 +41,7 @@ void launch_debug_forward(int solver, int n_envs, hipStream_t st, const DevModel
   hipLaunchKernelGGL(k_debug_forward<1>, dim3(n_envs), dim3(64), 0, st, m, P, B, out);
 }
 void launch_contacts(int solver, int n, hipStream_t st, const DevModel* m, const StepParams& P, const DevBuffers& B, const int* env_index, int forces,
-                     const TouchPairs& T, const ContactOut& O) {
+                     const TouchPairsT<4>& T, const ContactOut& O) {
   if (solver == 0) { launch_contacts_pgs(n, st, m, P, B, env_index, forces, T, O); return; }
   hipLaunchKernelGGL(k_contacts<1>, dim3((unsigned int)n), dim3(64), 0, st, m, P, B, env_index, forces, T, O);
 }

@@ -11,7 +11,7 @@ void launch_debug_forward_pgs(int n_envs, hipStream_t st, const DevModel* m, con
   hipLaunchKernelGGL(k_debug_forward<0>, dim3(n_envs), dim3(64), 0, st, m, P, B, out);
 }
 void launch_contacts_pgs(int n, hipStream_t st, const DevModel* m, const StepParams& P, const DevBuffers& B, const int* env_index, int forces,
-                         const TouchPairs& T, const ContactOut& O) {
+                         const TouchPairsT<4>& T, const ContactOut& O) {
   hipLaunchKernelGGL(k_contacts<0>, dim3((unsigned int)n), dim3(64), 0, st, m, P, B, env_index, forces, T, O);
 }
 }  // namespace so101

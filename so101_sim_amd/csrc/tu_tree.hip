@@ -23,7 +23,6 @@
 #endif
 
 #include "so101_tree_kernels.hpp"
-#include "so101_tree_contacts.hpp"
 #include "so101_tree_host.hpp"
 
 namespace TREE_NS {
@@ -347,23 +346,16 @@ int TAPI(tool_ik)(TreeHandle* s, const so101_tree_tool* tool, const so101_tree_i
   return hip_ok(s, hipGetLastError(), "k_tool_ik") ? SO101_OK : SO101_ERR_HIP;
 }
 
-// ---- contact sensing (so101_tree_contacts.hpp)
+// ---- contact sensing (k_tree_contacts of so101_tree_kernels.hpp)
 int TAPI(contacts)(TreeHandle* s, const int32_t* env_index, int n, int forces, const so101_tree_geom_pair* pairs, int npair, const so101_contact_out* out, void* stream) {
   if (!s) return SO101_ERR_ARG;
   const so101_contact_out* o = out;
   if (int rc = check_contact_arguments(s, "so101_tree_contacts", o, env_index != nullptr, n, s->n_envs, forces, pairs != nullptr, npair)) return rc;          // (so101_host.hpp)
-  TreeTouchPairs T{};
-  T.npair = npair;
-  for (int p = 0; p < npair; p++) {
-    for (int side = 0; side < 2; side++) {
-      const uint32_t* w = side ? pairs[p].b : pairs[p].a;
-      if (int rc = check_contact_group(s, "so101_tree_contacts", w, 8, p, side, s->hm.ngeom)) return rc;
-      memcpy(side ? T.b[p] : T.a[p], w, sizeof T.a[p]);
-    }
-  }
+  TouchPairsT<8> T{};
+  if (int rc = pack_touch_pairs(s, "so101_tree_contacts", pairs, npair, s->hm.ngeom, T)) return rc;
   if (!s->bound) { s->err = "so101_tree_contacts: state buffers not bound (call so101_tree_bind_state)"; return SO101_ERR_STATE; }
   GUARD_DEVICE(s);
-  ContactOut O{(int*)o->count, (int*)o->flags, (int*)o->geom, o->dist, o->pos, o->frame, o->force, (int*)o->pair_count, o->pair_dist, o->pair_normal, o->pair_force};
+  const ContactOut O = contact_out_of(o);
   // with forces entry i works in scratch slice i mod n_envs (env_index may repeat an env): at most n_envs entries per launch, the launches in
   // stream order; without forces the scratch is not touched and one launch serves any n
   const int chunk = forces ? s->n_envs : n;

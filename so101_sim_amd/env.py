@@ -24,6 +24,7 @@ from . import native
 from ._dmenv import BoundedArray, Array, StepType, TimeStep
 from .calibration import SO101Calibration
 from .model import scenes
+from . import contacts as _contacts
 from .tool_control import ToolControl
 
 DEFAULT_CONTROL_TIMESTEP = 0.02
@@ -117,7 +118,7 @@ class _PhysicsView:
         raise NotImplementedError("rendering is outside the MI355X hot path (SURVEY.md 8b)")
 
 
-class BatchedEnvironment(ToolControl):
+class BatchedEnvironment(ToolControl, _contacts.ContactSensing):
     def __init__(self, task: SO100HandOverTask, n_envs: int = 1, time_limit: float = float("inf"),
                  random_state=None, device=None, env_id_base: int = 0, solver_iterations: int = 0,
                  solver_tolerance: float = -1.0, settle_max_substeps: int = 1000, solver: str = "newton",
@@ -434,9 +435,11 @@ class BatchedEnvironment(ToolControl):
         offset = torch.tensor([float(x) for x in self.sim.cfg.action_offset], dtype=torch.float32, device=self.device)
         return q - offset
 
-    # ------------------------------------------------------------------ contact sensing (contacts.py)
+    # ------------------------------------------------------------------ contact sensing (contacts.py: ContactSensing)
+    _geom_limit = _contacts.MAX_GEOMS
+    _contact_capacity = native.MAXCON
+
     def _geom_groups(self):
-        from . import contacts as _contacts
         if getattr(self, "_groups", None) is None:
             from .model import blob as blobfmt
             self._groups = _contacts.so100_groups(self.meta, blobfmt.unpack(scenes.load_blob(self.task.object_name, "f32")[0]))
@@ -445,8 +448,7 @@ class BatchedEnvironment(ToolControl):
     def geom_group(self, spec):
         """A contacts.GeomGroup from a group name of the scene ("gripper", "arm", "props", "fixed_jaw_pads", "moving_jaw_pads", every body name),
         a geom name, an fnmatch pattern over the geom names, an iterable of geom ids or a GeomGroup."""
-        from . import contacts as _contacts
-        return _contacts.resolve(spec, self._geom_groups(), self.meta)
+        return self._geom_group(spec)
 
     def contacts(self, env_ids=None, forces: bool = False):
         """The contact lists of the envs `env_ids` (None = all) at their current state, on the GPU (so101_contacts): a
@@ -455,37 +457,14 @@ class BatchedEnvironment(ToolControl):
         normal geom1 -> geom2 and two tangents, MuJoCo's contact.frame) and, with forces=True, force [n, 64, 6] (mj_contactForce), else None.
         Slots beyond count hold geoms -1, dist +inf, zeros.  The forces are those of a forward pass at the current state (constraint rows and
         solve, warmstart read and left alone), not the impulses of the last substep; without forces only kinematics and collision run."""
-        from . import contacts as _contacts
-        torch = self.torch
-        idx, n = self._env_index(env_ids)
-        C = native.MAXCON
-        e = lambda *s, dt=torch.float32: torch.empty(*s, dtype=dt, device=self.device)
-        rep = _contacts.ContactReport(e(n, dt=torch.int32), e(n, dt=torch.int32), e(n, C, 2, dt=torch.int32), e(n, C), e(n, C, 3), e(n, C, 3, 3),
-                                      e(n, C, 6) if forces else None)
-        out = native.ContactOut(**{k: (t.data_ptr() if t is not None else None) for k, t in rep._asdict().items()})
-        self.sim.contacts(idx.data_ptr() if idx is not None else None, n, forces, None, out, self._stream())
-        return rep
+        return self._contacts(env_ids, forces)
 
     def touch(self, pairs, env_ids=None, forces: bool = False):
         """Who touches whom: `pairs` is a sequence of at most 16 (a, b), each side anything geom_group() takes.  Per env of `env_ids` (None = all)
         and pair, reduced on the GPU from the env's contact list: a contacts.TouchReport of count [n, npair] int32 (contacts with one geom in a
         and the other in b), touching = count > 0, dist [n, npair] (the smallest, +inf without a contact) and, with forces=True,
         normal_force [n, npair] (sum of the normal forces) and force [n, npair, 3] (the net world-frame force ON group a), else None."""
-        from . import contacts as _contacts
-        torch = self.torch
-        pairs = list(pairs)
-        if not 1 <= len(pairs) <= _contacts.MAX_PAIRS:
-            raise ValueError(f"touch takes 1 .. {_contacts.MAX_PAIRS} pairs, got {len(pairs)}")
-        masks = [(self.geom_group(a).mask(), self.geom_group(b).mask()) for a, b in pairs]
-        idx, n = self._env_index(env_ids)
-        P = len(masks)
-        e = lambda *s, dt=torch.float32: torch.empty(*s, dtype=dt, device=self.device)
-        count, dist = e(n, P, dt=torch.int32), e(n, P)
-        normal, force = (e(n, P), e(n, P, 3)) if forces else (None, None)
-        out = native.ContactOut(pair_count=count.data_ptr(), pair_dist=dist.data_ptr(), pair_normal=normal.data_ptr() if forces else None,
-                                pair_force=force.data_ptr() if forces else None)
-        self.sim.contacts(idx.data_ptr() if idx is not None else None, n, forces, masks, out, self._stream())
-        return _contacts.TouchReport(count, count > 0, dist, normal, force)
+        return self._touch(pairs, env_ids, forces)
 
     def events(self, clear: bool = False) -> dict:
         """Counts since creation (or the last clear) of env-steps / env-resets that raised a flag: contact or candidate

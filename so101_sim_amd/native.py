@@ -101,23 +101,15 @@ class ContactOut(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in CONTACT_OUT_FIELDS]
 
 
-def geom_pair_array(pairs):
-    """((a words[4], b words[4]), ...) as the so101_geom_pair array of so101_contacts"""
-    arr = (GeomPair * max(len(pairs), 1))()
-    for k, (a, b) in enumerate(pairs):
-        arr[k].a[:] = [int(x) & 0xFFFFFFFF for x in a]
-        arr[k].b[:] = [int(x) & 0xFFFFFFFF for x in b]
-    return arr
-
-
 class TreeGeomPair(C.Structure):
     """so101_tree_geom_pair of include/so101.h: two 256-bit geom masks"""
     _fields_ = [("a", C.c_uint32 * 8), ("b", C.c_uint32 * 8)]
 
 
-def tree_geom_pair_array(pairs):
-    """((a words[8], b words[8]), ...) as the so101_tree_geom_pair array of so101_tree_contacts"""
-    arr = (TreeGeomPair * max(len(pairs), 1))()
+def geom_pair_array(pairs, words: int = 4):
+    """((a words, b words), ...) as the so101_geom_pair array of so101_contacts (words = 4) or the so101_tree_geom_pair array of
+    so101_tree_contacts (words = 8)"""
+    arr = ({4: GeomPair, 8: TreeGeomPair}[words] * max(len(pairs), 1))()
     for k, (a, b) in enumerate(pairs):
         arr[k].a[:] = [int(x) & 0xFFFFFFFF for x in a]
         arr[k].b[:] = [int(x) & 0xFFFFFFFF for x in b]
@@ -535,5 +527,5 @@ class TreeSim:
     def contacts(self, env_index, n: int, forces: bool, pairs, out: ContactOut, stream=0):
         """so101_tree_contacts; pairs: sequence of (a words[8], b words[8]) geom masks; env_index and the fields of `out`: raw device addresses or
         None.  The per-contact fields of `out` have max_contacts slots per entry."""
-        arr = tree_geom_pair_array(pairs) if pairs else None
+        arr = geom_pair_array(pairs, 8) if pairs else None
         self._check(self.L.so101_tree_contacts(self.h, env_index, int(n), int(bool(forces)), arr, len(pairs) if pairs else 0, C.byref(out), stream), "so101_tree_contacts")

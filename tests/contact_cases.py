@@ -1,6 +1,7 @@
 """Shared cases of the contact-interface tests (so101_contacts, include/so101.h): the raw call on an ArraySim of either backend, the
 states, the group pairs, and the checks both backends run - tests/test_contacts_emu.py on 4 states through the emulated build,
-tests/test_contacts_gpu.py on all 24 on the MI355X.
+tests/test_contacts_gpu.py on all 24 on the MI355X.  What does not depend on the engine serves the general-tree engine's tests as well
+(tests/tree_contact_cases.py): raw_contacts, check_touch, force_errors, bound4, the frame, swap, outside and row checks.
 
 The pairs.  `gripper | object`, `arm | table`, `fixed_jaw_pads | object`, `object | container`, `arm | arm` and `gripper | arm`, whose
 groups overlap; no state of the fixture has a jaw pad on the object or the object on the container (those two pairs are the
@@ -11,6 +12,8 @@ pair whose two groups are the same set.
 
 The force-sum bound: 1e-5 * sum |f_k| + 1e-7 - 64 terms of fp32 summation plus a 3 x 3 rotation, a few 1e-7 relative each."""
 from __future__ import annotations
+
+import math
 
 import numpy as np
 
@@ -24,7 +27,7 @@ FREE_STATE = 11                    # the fixture's state without any contact
 PAIR_SPECS = (("gripper", "object"), ("arm", "table"), ("fixed_jaw_pads", "object"), ("object", "container"), ("arm", "arm"), ("gripper", "arm"),
               ("fixed_jaw_pads", "table"))
 FIELDS = native.CONTACT_OUT_FIELDS
-_SHAPE = dict(count=(), flags=(), geom=(C, 2), dist=(C,), pos=(C, 3), frame=(C, 9), force=(C, 6))
+_PER_CONTACT = dict(geom=(2,), dist=(), pos=(3,), frame=(9,), force=(6,))          # [n, capacity] + this; count and flags are [n]
 _INT = ("count", "flags", "geom", "pair_count")
 GEOMETRY = ("count", "flags", "geom", "dist", "pos", "frame")
 PAIR_GEOMETRY, PAIR_FORCES = ("pair_count", "pair_dist"), ("pair_normal", "pair_force")
@@ -54,23 +57,28 @@ def load(sim, Q, V, A, W):
     return sim
 
 
-def raw_contacts(sim, n=None, env_index=None, forces=False, pairs=(), want=None):
-    """so101_contacts on an ArraySim -> dict of numpy arrays.  `want`: the outputs asked for (None: everything the call allows).  The
-    outputs start as 7e7 / -7, so an entry the kernel does not write fails every check."""
+def raw_contacts(sim, n=None, env_index=None, forces=False, pairs=(), want=None, capacity=None):
+    """so101_contacts on an ArraySim / so101_tree_contacts on a TreeArraySim -> dict of numpy arrays, the per-contact ones [n, capacity, k]
+    (`capacity` None: the handle's own - a tree handle's max_contacts, else native.MAXCON).  `want`: the outputs asked for (None: everything
+    the call allows).  The outputs start as 7e7 / -7, so an element the kernel does not write fails every check."""
     n = sim.N if n is None else n
     P = len(pairs)
+    cap = capacity if capacity is not None else getattr(sim.sim, "max_contacts", C)
     if want is None:
         want = [k for k in FIELDS if (forces or k not in ("force",) + PAIR_FORCES) and (P or not k.startswith("pair_"))]
+    gpu = sim.backend == "gpu"
     arrs = {}
     for k in want:
-        shape = (n,) + ((P,) + ((3,) if k == "pair_force" else ()) if k.startswith("pair_") else _SHAPE[k])
+        if k.startswith("pair_"):
+            shape = (n, P) + ((3,) if k == "pair_force" else ())
+        else:
+            shape = (n, cap) + _PER_CONTACT[k] if k in _PER_CONTACT else (n,)
         dt, fill = (np.int32, -7) if k in _INT else (np.float32, 7e7)
-        arrs[k] = sim.torch.full(shape, fill, dtype=sim.torch.int32 if dt == np.int32 else sim.torch.float32, device=sim.dev) if sim.backend == "gpu" \
-            else np.full(shape, fill, dtype=dt)
+        arrs[k] = sim.torch.full(shape, fill, dtype=sim.torch.int32 if dt == np.int32 else sim.torch.float32, device=sim.dev) if gpu else np.full(shape, fill, dtype=dt)
     idx = None
     if env_index is not None:
         idx = np.ascontiguousarray(env_index, dtype=np.int32)
-        idx = sim.torch.as_tensor(idx).to(sim.dev) if sim.backend == "gpu" else idx
+        idx = sim.torch.as_tensor(idx).to(sim.dev) if gpu else idx
     out = native.ContactOut(**{k: sim.ptr(a) for k, a in arrs.items()})
     sim.sim.contacts(sim.ptr(idx) if idx is not None else None, n, forces, list(pairs), out, sim.stream())
     return {k: sim._get(a) for k, a in arrs.items()}
@@ -117,21 +125,22 @@ def check_frames(rep):
     assert worst_o <= 1e-6 and worst_c <= 1e-6, (worst_o, worst_c)
 
 
-def check_touch(rep, masks):
-    """the pair outputs of `rep` (a report with forces, pairs = masks) against the fp64 reduction of its own per-contact output"""
+def check_touch(rep, masks, k=1e-5):
+    """the pair outputs of `rep` (a report with forces, pairs = masks) against the fp64 reduction of its own per-contact output; the sums
+    within k * sum |f_j| + 1e-7 (the module docstring; tests/tree_contact_cases.py: SUM_BOUND_K)"""
     worst = 0.0
     seen = np.zeros(len(masks), dtype=bool)
     for e in range(len(rep["count"])):
-        k = int(rep["count"][e])
-        cnt, dmin, normal, net, scale = cr.reduce_pairs(masks, rep["geom"][e, :k], rep["dist"][e, :k], rep["frame"][e, :k], rep["force"][e, :k])
+        m = int(rep["count"][e])
+        cnt, dmin, normal, net, scale = cr.reduce_pairs(masks, rep["geom"][e, :m], rep["dist"][e, :m], rep["frame"][e, :m], rep["force"][e, :m])
         assert np.array_equal(rep["pair_count"][e], cnt), (e, rep["pair_count"][e], cnt)
         assert np.array_equal(rep["pair_dist"][e].astype(np.float64), dmin), (e, rep["pair_dist"][e], dmin)
-        bound = 1e-5 * scale + 1e-7
+        bound = k * scale + 1e-7
         en, ef = np.abs(rep["pair_normal"][e] - normal), np.abs(rep["pair_force"][e] - net).max(axis=1)
         worst = max(worst, (np.maximum(en, ef) / bound).max())
         assert np.all(en <= bound) and np.all(ef <= bound), (e, en, ef, bound)
         seen |= cnt > 0
-    print(f"touch sums vs fp64: worst error / bound {worst:.3e}; pairs with contacts {seen.tolist()}")
+    print(f"touch sums vs fp64 (k = {k:g}): worst error / bound {worst:.3e}; pairs with contacts {seen.tolist()}")
     return seen
 
 
@@ -169,3 +178,27 @@ def check_rows_equal(rep, rows, ref, ref_rows):
     for f in rep:
         if f in ref:
             assert same_bits(rep[f][list(rows)], ref[f][list(ref_rows)]), f
+
+
+def force_errors(rep, e, f_ref):
+    """(per contact, per geom pair) error of entry e over its largest reference normal force: max over contacts and the six entries of
+    |f - f_ref|, and max over the touching geom pairs of |net - net_ref|, net = sum over the pair's contacts of R^T f[0:3]"""
+    k = int(rep["count"][e])
+    if k == 0:
+        return 0.0, 0.0
+    f = rep["force"][e, :k].astype(np.float64)
+    scale = f_ref[:, 0].max()
+    nets, refs = {}, {}
+    for i in range(k):
+        key = (int(rep["geom"][e, i, 0]), int(rep["geom"][e, i, 1]))
+        R = rep["frame"][e, i].astype(np.float64).reshape(3, 3)
+        nets[key] = nets.get(key, 0.0) + R.T @ f[i, :3]
+        refs[key] = refs.get(key, 0.0) + cr.make_frame(R[0]).T @ f_ref[i, :3]          # (the oracle completes the injected normal itself)
+    return np.abs(f - f_ref).max() / scale, max(np.abs(nets[key] - refs[key]).max() for key in nets) / scale
+
+
+def bound4(x):
+    """4 x, rounded up to one significant digit"""
+    y = 4.0 * x
+    p = 10.0 ** math.floor(math.log10(y))
+    return math.ceil(y / p - 1e-9) * p

@@ -10,8 +10,6 @@ figures per env, both over max_k f_ref[k][0], the largest normal force of the st
 FORCE_MEASURED holds the worst of each over the 24 states as measured on the MI355X (profiles/README.md, "Contact sensing"); the
 tests assert 4 x that, rounded up to one significant digit - the margin for fp32 reassociation across compilers and for a solver
 that stops at its tolerance on ill-conditioned multi-contact patches."""
-import math
-
 import numpy as np
 import pytest
 
@@ -23,13 +21,6 @@ from tests.simharness import ArraySim
 
 pytestmark = pytest.mark.gpu
 FORCE_MEASURED = dict(contact=1.878e-4, pair=2.028e-4)  # worst figures of the 24 states on the MI355X (states 8 and 7): bounds 8e-4 and 9e-4
-
-
-def _bound(x):
-    """4 x, rounded up to one significant digit"""
-    y = 4.0 * x
-    p = 10.0 ** math.floor(math.log10(y))
-    return math.ceil(y / p - 1e-9) * p
 
 
 def _batch(blobs, golden, solver):
@@ -107,30 +98,14 @@ def test_capacity_rule_is_the_oracles(blobs):
     assert loose <= max(1, 0.05 * total) and witness <= max(2, 0.1 * total), (loose, witness, total)          # (the shares check_contact_capacity_mirrored asserts on this state)
 
 
-def _force_errors(rep, e, f_ref):
-    """(per contact, per geom pair) error of env e over its largest reference normal force"""
-    k = int(rep["count"][e])
-    if k == 0:
-        return 0.0, 0.0
-    f = rep["force"][e, :k].astype(np.float64)
-    scale = f_ref[:, 0].max()
-    nets, refs = {}, {}
-    for i in range(k):
-        key = (int(rep["geom"][e, i, 0]), int(rep["geom"][e, i, 1]))
-        R = rep["frame"][e, i].astype(np.float64).reshape(3, 3)
-        nets[key] = nets.get(key, 0.0) + R.T @ f[i, :3]
-        refs[key] = refs.get(key, 0.0) + cr.make_frame(R[0]).T @ f_ref[i, :3]          # (the oracle completes the injected normal itself)
-    return np.abs(f - f_ref).max() / scale, max(np.abs(nets[key] - refs[key]).max() for key in nets) / scale
-
-
 def test_forces_match_the_oracle_on_the_kernels_list(newton, oracle_forces):
     worst = np.zeros(2)
     for e in range(24):
-        err = _force_errors(newton["rep"], e, oracle_forces[e])
+        err = cc.force_errors(newton["rep"], e, oracle_forces[e])
         print(f"state {e:2d}: {int(newton['rep']['count'][e]):2d} contacts, force error per contact {err[0]:.3e}, per geom pair {err[1]:.3e}")
         worst = np.maximum(worst, err)
     print(f"worst of the 24 states: per contact {worst[0]:.3e}, per geom pair {worst[1]:.3e}")
-    assert worst[0] <= _bound(FORCE_MEASURED["contact"]) and worst[1] <= _bound(FORCE_MEASURED["pair"]), worst
+    assert worst[0] <= cc.bound4(FORCE_MEASURED["contact"]) and worst[1] <= cc.bound4(FORCE_MEASURED["pair"]), worst
 
 
 def test_resting_and_free_space_states(blobs, golden):
@@ -165,7 +140,7 @@ def test_resting_and_free_space_states(blobs, golden):
     err_f = np.abs(touch.force[0, :2].cpu().numpy() - net_ref).max() / scale
     print(f"resting props: {k} contacts, object | table normal force {float(touch.normal_force[0, 0]):.5f} N (oracle {normal_ref[0]:.5f}), error {err_n:.3e}, net force error {err_f:.3e}")
     assert bool(touch.touching[0, 0]) and bool(touch.touching[0, 1]) and k >= int(touch.count[0, :2].sum())
-    assert err_n <= _bound(FORCE_MEASURED["pair"]) and err_f <= _bound(FORCE_MEASURED["pair"])
+    assert err_n <= cc.bound4(FORCE_MEASURED["pair"]) and err_f <= cc.bound4(FORCE_MEASURED["pair"])
     assert net_ref[0, 2] > 0 and abs(float(touch.force[0, 0, 2]) - float(touch.normal_force[0, 0])) <= 1e-3 * float(touch.normal_force[0, 0])      # the table pushes the object up
 
 

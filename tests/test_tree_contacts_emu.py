@@ -38,7 +38,7 @@ def test_argument_and_state_errors(kind, build, capacity):
     force, pf = np.zeros((4, capacity, 6), np.float32), np.zeros((4, 16, 3), np.float32)
     idx = np.zeros(4, np.int32)
     w8 = lambda *bits: tuple(sum(1 << (g & 31) for g in bits if g >> 5 == k) for k in range(8))
-    one = native.tree_geom_pair_array([(w8(0), w8(1))])
+    one = native.geom_pair_array([(w8(0), w8(1))], 8)
     P = lambda a: None if a is None else a.ctypes.data
 
     def call(hh=h, idx=None, n=2, forces=0, pairs=None, npair=0, out="default", **fields):
@@ -58,12 +58,12 @@ def test_argument_and_state_errors(kind, build, capacity):
     for f in ("pair_count", "pair_dist", "pair_normal", "pair_force"):
         assert call(forces=1, **{f: pn}) == -1 and "npair == 0" in err(), f
     for side in (0, 1):
-        empty = native.tree_geom_pair_array([(w8(0), w8(1)), (w8(), w8(2))[::1 if side == 0 else -1]])
+        empty = native.geom_pair_array([(w8(0), w8(1)), (w8(), w8(2))[::1 if side == 0 else -1]], 8)
         assert call(pairs=empty, npair=2, pair_count=pc) == -1 and f"pair 1, group {'ab'[side]} is empty" in err()
-        beyond = native.tree_geom_pair_array([(w8(0), w8(ngeom))[::1 if side == 1 else -1]])
+        beyond = native.geom_pair_array([(w8(0), w8(ngeom))[::1 if side == 1 else -1]], 8)
         assert call(pairs=beyond, npair=1, pair_count=pc) == -1 and f"bit {ngeom} is at or beyond ngeom = {ngeom}" in err() and err().startswith("so101_tree_contacts: pair 0")
-    assert call(pairs=native.tree_geom_pair_array([(w8(ngeom - 1), w8(0))]), npair=1, pair_count=pc) == 0          # the last geom is a member like any other
-    assert call(pairs=native.tree_geom_pair_array([(w8(0), w8(255))]), npair=1, pair_count=pc) == -1 and "bit 255" in err()      # the eighth word is read
+    assert call(pairs=native.geom_pair_array([(w8(ngeom - 1), w8(0))], 8), npair=1, pair_count=pc) == 0          # the last geom is a member like any other
+    assert call(pairs=native.geom_pair_array([(w8(0), w8(255))], 8), npair=1, pair_count=pc) == -1 and "bit 255" in err()      # the eighth word is read
     assert call(force=force) == -1 and "need forces" in err()
     assert call(pairs=one, npair=1, pair_normal=pn) == -1 and "need forces" in err()
     assert call(pairs=one, npair=1, pair_force=pf) == -1 and "need forces" in err()
@@ -98,7 +98,7 @@ def test_geometry_and_forces_against_the_oracle(emu):
 
 
 def test_touch_reduction_and_swap(emu):
-    seen = tc.check_touch(emu["rep"], emu["masks"], 32)
+    seen = tc.check_touch(emu["rep"], emu["masks"], tc.SUM_BOUND_K[32])
     assert seen.tolist() == tc.SEEN["handover"], seen
     tc.check_quiet(emu["rep"], seen)
     cc.check_swap(emu["rep"], emu["swapped"], emu["masks"])
@@ -124,7 +124,7 @@ def test_dining_state_emulated():
     assert int(out["rep"]["count"][0]) == tc.DINING_COUNTS[1] > 128
     cc.check_frames(out["rep"])
     tc.check_geometry(out["geo"], tc.oracle_lists("dining", (1,)))
-    seen = tc.check_touch(out["rep"], out["masks"], 64)
+    seen = tc.check_touch(out["rep"], out["masks"], tc.SUM_BOUND_K[64])
     assert seen.tolist() == tc.SEEN["dining"], seen
 
 

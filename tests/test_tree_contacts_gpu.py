@@ -75,7 +75,7 @@ def test_forces_match_the_oracle_on_the_kernels_list(batch):
 
 def test_touch_reduction_and_swap(batch):
     rep, masks, sim = batch["rep"], batch["masks"], batch["sim"]
-    seen = tc.check_touch(rep, masks, batch["build"])
+    seen = tc.check_touch(rep, masks, tc.SUM_BOUND_K[batch["build"]])
     assert seen.tolist() == tc.SEEN[batch["kind"]], seen
     tc.check_quiet(rep, seen)
     swapped = tc.raw_contacts(sim, forces=True, pairs=[(y, x) for x, y in masks], want=tc.PAIR_GEOMETRY + tc.PAIR_FORCES)

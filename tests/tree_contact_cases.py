@@ -40,6 +40,7 @@ from so101_sim_amd import contacts as ct, native
 from so101_sim_amd.model import blob as blobfmt
 from so101_sim_amd.model import scenes
 from tests import contact_cases as cc, contact_ref as cr
+from tests.contact_cases import bound4, check_touch, force_errors, raw_contacts          # (one copy for both engines)
 
 PAIR_SPECS = (("grippers", "object"), ("right_gripper", "object"), ("arms", "table"), ("object", "container"), ("props", "table"), ("arms", "arms"),
               ("left_gripper", "container"))
@@ -52,8 +53,6 @@ EMU_HANDOVER = (0, 6)                                           # a resting and 
 DINING_SEED, DINING_LANDING_SUBSTEPS = 1, 45
 DINING_COUNTS = [48, 140]
 FIELDS = native.CONTACT_OUT_FIELDS
-_INT = ("count", "flags", "geom", "pair_count")
-_PER_CONTACT = dict(geom=2, dist=0, pos=3, frame=9, force=6)
 GEOMETRY = cc.GEOMETRY
 PAIR_GEOMETRY, PAIR_FORCES = cc.PAIR_GEOMETRY, cc.PAIR_FORCES
 same_bits = cc.same_bits
@@ -142,32 +141,6 @@ def load(sim, Q, V, CT, W):
     return sim
 
 
-def raw_contacts(sim, n=None, env_index=None, forces=False, pairs=(), want=None):
-    """so101_tree_contacts on a TreeArraySim -> dict of numpy arrays, the per-contact ones [n, C, k] with C = the handle's capacity.
-    `want`: the outputs asked for (None: everything the call allows).  The outputs start as 7e7 / -7, so an element the kernel does not
-    write fails every check."""
-    n = sim.N if n is None else n
-    P, C = len(pairs), sim.sim.max_contacts
-    if want is None:
-        want = [k for k in FIELDS if (forces or k not in ("force",) + PAIR_FORCES) and (P or not k.startswith("pair_"))]
-    gpu = sim.backend == "gpu"
-    arrs = {}
-    for k in want:
-        if k.startswith("pair_"):
-            shape = (n, P) + ((3,) if k == "pair_force" else ())
-        else:
-            shape = (n,) + ((C,) + ((_PER_CONTACT[k],) if _PER_CONTACT[k] else ()) if k in _PER_CONTACT else ())
-        dt, fill = (np.int32, -7) if k in _INT else (np.float32, 7e7)
-        arrs[k] = sim.torch.full(shape, fill, dtype=sim.torch.int32 if dt == np.int32 else sim.torch.float32, device=sim.dev) if gpu else np.full(shape, fill, dtype=dt)
-    idx = None
-    if env_index is not None:
-        idx = np.ascontiguousarray(env_index, dtype=np.int32)
-        idx = sim.torch.as_tensor(idx).to(sim.dev) if gpu else idx
-    out = native.ContactOut(**{k: sim.ptr(a) for k, a in arrs.items()})
-    sim.sim.contacts(sim.ptr(idx) if idx is not None else None, n, forces, list(pairs), out, sim.stream())
-    return {k: sim._get(a) for k, a in arrs.items()}
-
-
 def run_batch(sim, masks):
     """ONE pass of what most tests read: the report with and without forces, the state before and after, the stage dump"""
     before = [sim._get(a) for a in (sim.qpos, sim.qvel, sim.ctrl, sim.warm)]
@@ -224,45 +197,10 @@ def check_geometry(rep, lists):
     return total
 
 
-def check_touch(rep, masks, build):
-    """the pair outputs of `rep` (a report with forces, pairs = masks) against the fp64 reduction of its own per-contact output"""
-    worst = 0.0
-    seen = np.zeros(len(masks), dtype=bool)
-    for e in range(len(rep["count"])):
-        k = int(rep["count"][e])
-        cnt, dmin, normal, net, scale = cr.reduce_pairs(masks, rep["geom"][e, :k], rep["dist"][e, :k], rep["frame"][e, :k], rep["force"][e, :k])
-        assert np.array_equal(rep["pair_count"][e], cnt), (e, rep["pair_count"][e], cnt)
-        assert np.array_equal(rep["pair_dist"][e].astype(np.float64), dmin), (e, rep["pair_dist"][e], dmin)
-        bound = SUM_BOUND_K[build] * scale + 1e-7
-        en, ef = np.abs(rep["pair_normal"][e] - normal), np.abs(rep["pair_force"][e] - net).max(axis=1)
-        worst = max(worst, (np.maximum(en, ef) / bound).max())
-        assert np.all(en <= bound) and np.all(ef <= bound), (e, en, ef, bound)
-        seen |= cnt > 0
-    print(f"touch sums vs fp64 (build {build}): worst error / bound {worst:.3e}; pairs with contacts {seen.tolist()}")
-    return seen
-
-
 def check_quiet(rep, seen):
     quiet = ~np.asarray(seen)
     assert np.all(rep["pair_count"][:, quiet] == 0) and np.all(np.isposinf(rep["pair_dist"][:, quiet]))
     assert np.all(rep["pair_normal"][:, quiet] == 0) and np.all(rep["pair_force"][:, quiet] == 0)
-
-
-def force_errors(rep, e, f_ref):
-    """(per contact, per geom pair) error of entry e over its largest reference normal force: max over contacts and the six entries of
-    |f - f_ref|, and max over the touching geom pairs of |net - net_ref|, net = sum over the pair's contacts of R^T f[0:3]"""
-    k = int(rep["count"][e])
-    if k == 0:
-        return 0.0, 0.0
-    f = rep["force"][e, :k].astype(np.float64)
-    scale = f_ref[:, 0].max()
-    nets, refs = {}, {}
-    for i in range(k):
-        key = (int(rep["geom"][e, i, 0]), int(rep["geom"][e, i, 1]))
-        R = rep["frame"][e, i].astype(np.float64).reshape(3, 3)
-        nets[key] = nets.get(key, 0.0) + R.T @ f[i, :3]
-        refs[key] = refs.get(key, 0.0) + cr.make_frame(R[0]).T @ f_ref[i, :3]          # (the oracle completes the injected normal itself)
-    return np.abs(f - f_ref).max() / scale, max(np.abs(nets[key] - refs[key]).max() for key in nets) / scale
 
 
 def oracle_forces(kind, rep, which=None):
@@ -277,11 +215,3 @@ def oracle_forces(kind, rep, which=None):
         out.append(cr.oracle_contact_forces(o) if int(rep["count"][e]) else np.zeros((0, 6)))
     o.inject_contacts([])
     return out
-
-
-def bound4(x):
-    """4 x, rounded up to one significant digit"""
-    import math
-    y = 4.0 * x
-    p = 10.0 ** math.floor(math.log10(y))
-    return math.ceil(y / p - 1e-9) * p
