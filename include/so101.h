@@ -35,7 +35,7 @@ extern "C" {
 
 #define SO101_ABI_VERSION 10     /* 10: so101_tree_last_plan, and (additions that change nothing older, so the number stays) the cameras: so101_camera,
                                     so101_set_hull_planes, so101_render, so101_tree_set_hull_planes, so101_tree_render, and Cartesian tool control: so101_tool, so101_ik_config, so101_ik_default_config,
-                                    so101_tool_pose, so101_tool_ik, and the same for the general-tree engine: so101_tree_tool, so101_tree_ik_config, so101_tree_tool_chain,
+                                    so101_tool_pose, so101_tool_ik, proximity sensing: so101_proximity_out, so101_proximity, and the same (tool control) for the general-tree engine: so101_tree_tool, so101_tree_ik_config, so101_tree_tool_chain,
                                     so101_tree_ik_default_config, so101_tree_tool_pose, so101_tree_tool_ik; 9: so101_tree_config gains the observation delays, so101_tree_bind_physics_state; 8: the general-tree engine (so101_tree_*) */
 #define SO101_OBS_DIM 18      /* joints_pos(6, delayed) | undelayed_joints_pos(6) | commanded_joints_pos(6) */
 #define SO101_ACT_DIM 6
@@ -383,6 +383,39 @@ typedef struct {
 int so101_contacts(so101_sim* sim, const int32_t* env_index, int n, int forces,
                    const so101_geom_pair* pairs /* HOST, npair of them */, int npair,
                    const so101_contact_out* out, void* hip_stream);
+
+/* ---- proximity sensing (csrc/so101_proximity.hpp): how far apart two groups of geoms are while they do not touch - MuJoCo's mj_geomDistance /
+ * <distance> sensor, batched.  Per entry i and pair p: over every geom pair of the model's admitted pair list (the list the broadphase walks:
+ * no same-body and no excluded pairs) with one geom in group a and the other in b, the smallest signed distance.  Separated geoms: the
+ * Euclidean gap of the surfaces (GJK, spheres and capsules as core plus radius), >= 0.  Penetrating geoms: the smallest contact dist of the
+ * step's narrowphase for that geom pair (< 0, the number so101_contacts' pair_dist gives), flags bit 1.  geom: the winning geom pair, the
+ * a-side geom first.  point: the closest point on the a-side geom and on the b-side geom, world frame; for a penetrating pair the contact
+ * position offset by -+ dist / 2 along the normal.  normal: unit vector from the a point to the b point; for a penetrating pair the contact
+ * normal oriented from a to b.  Nothing below max_dist (or no admitted pair): dist = max_dist, geom -1, point and normal 0, flags bit 4 (what
+ * mj_geomDistance does with distmax).  flags: 1 penetrating, 2 the distance iteration hit its cap on the winning pair (the value is an upper
+ * bound), 4 nothing within max_dist, 8 (with 4) the entry's env index is outside the batch.  Ties go to the pair that comes first in the
+ * pair list.  queries: exact pair queries run for the entry and pair (the rest was culled by bounding spheres).
+ *
+ * q: DEVICE [n][6] arm joint angles (qpos[0:6], the convention of so101_tool_pose) or NULL: entry i is evaluated with the props of env
+ * env_index[i] where they are and the arm at q[i]; nothing bound is read for the arm's angles then and nothing bound is ever written - qpos, qvel,
+ * ctrl and the warmstart stay as they are.  env_index may repeat an env: K waypoints against one env in one call.  An entry's output bits
+ * depend on its env's state, q[i], its pair and max_dist only.  Asynchronous on `hip_stream`.  SO100 engine only; an addition: the ABI number stays.
+ *
+ * env_index: DEVICE array of n env indices, or NULL for envs 0 .. n - 1.  pairs: HOST array of npair pairs, copied.  out: HOST struct of
+ * DEVICE pointers.  SO101_ERR_ARG (with a message in so101_last_error): NULL handle or out; no output pointer at all; n outside 1 .. 2^26, or
+ * n > n_envs with env_index == NULL; npair outside 1 .. SO101_TOUCH_MAX_PAIRS; NULL pairs; an empty group; a group bit at or beyond ngeom;
+ * max_dist not a finite number in (0, 10].  SO101_ERR_STATE: no state bound. */
+typedef struct {
+  float*   dist;     /* [n][npair] */
+  int32_t* geom;     /* [n][npair][2]    a-side geom, b-side geom; -1 with flags bit 4 */
+  float*   point;    /* [n][npair][2][3] */
+  float*   normal;   /* [n][npair][3] */
+  int32_t* flags;    /* [n][npair] */
+  int32_t* queries;  /* [n][npair] */
+} so101_proximity_out;     /* DEVICE pointers, any may be NULL, not all */
+int so101_proximity(so101_sim* sim, const int32_t* env_index, int n, const float* q /* DEVICE [n][6] or NULL */,
+                    const so101_geom_pair* pairs /* HOST, npair of them */, int npair, float max_dist,
+                    const so101_proximity_out* out, void* hip_stream);
 
 const char* so101_last_error(const so101_sim* sim);
 

@@ -889,6 +889,32 @@ int so101_contacts(so101_sim* s, const int32_t* env_index, int n, int forces, co
   return SO101_OK;
 }
 
+// ---- proximity sensing (csrc/so101_proximity.hpp; the groups are checked and packed like so101_contacts')
+int so101_proximity(so101_sim* s, const int32_t* env_index, int n, const float* q, const so101_geom_pair* pairs, int npair, float max_dist,
+                    const so101_proximity_out* out, void* stream) {
+  if (!s) return SO101_ERR_ARG;
+  const so101_proximity_out* o = out;
+  const char* bad = nullptr;
+  if (!o) bad = "NULL out";
+  else if (!o->dist && !o->geom && !o->point && !o->normal && !o->flags && !o->queries) bad = "no output (every pointer of out is NULL)";
+  else if (n < 1 || n > (1 << 26)) bad = "n must be 1 .. 2^26";
+  else if (!env_index && n > s->n_envs) bad = "n exceeds the envs of the handle";
+  else if (npair < 1 || npair > SO101_TOUCH_MAX_PAIRS) bad = "npair must be 1 .. 16";
+  else if (!pairs) bad = "NULL pairs";
+  if (bad) { s->err = std::string("so101_proximity: ") + bad; return SO101_ERR_ARG; }
+  const int ngeom = s->hm.ngeom;
+  if (ngeom > 128) { s->err = "so101_proximity: the model has more than 128 geoms (a group mask has 128 bits)"; return SO101_ERR_STATE; }
+  TouchPairsT<4> T{};
+  if (int rc = pack_touch_pairs(s, "so101_proximity", pairs, npair, ngeom, T)) return rc;
+  if (!(std::isfinite(max_dist) && max_dist > 0.f && max_dist <= 10.f)) { s->err = "so101_proximity: max_dist must be a finite number above 0 and at most 10"; return SO101_ERR_ARG; }
+  if (!s->bound) { s->err = "so101_proximity: state buffers not bound (call so101_bind_state)"; return SO101_ERR_STATE; }
+  GUARD_DEVICE(s);
+  so101::launch_proximity(n, (hipStream_t)stream, s->dm, make_params(s), s->buf, (const int*)env_index, q, T, max_dist,
+                          ProxOut{o->dist, (int*)o->geom, o->point, o->normal, (int*)o->flags, (int*)o->queries});
+  LAUNCH_CHECK(s, "k_proximity");
+  return SO101_OK;
+}
+
 int so101_debug_stages(so101_sim* s, uint32_t* stage, void* stream) {
   if (!s || !stage) return SO101_ERR_ARG;
   GUARD_DEVICE(s);

@@ -30,6 +30,9 @@ void launch_debug_forward(int solver, int n_envs, hipStream_t st, const DevModel
 // contact sensing (so101_contacts.hpp): one wavefront per reported env, n of them; env_index NULL = envs 0 .. n - 1
 void launch_contacts(int solver, int n, hipStream_t st, const DevModel* m, const StepParams& P, const DevBuffers& B, const int* env_index, int forces,
                      const TouchPairsT<4>& T, const ContactOut& O);
+// proximity sensing (so101_proximity.hpp): one wavefront per (entry, pair), n * T.npair of them; q NULL = the bound arm angles
+void launch_proximity(int n, hipStream_t st, const DevModel* m, const StepParams& P, const DevBuffers& B, const int* env_index, const float* q,
+                      const TouchPairsT<4>& T, float max_dist, const ProxOut& O);
 void launch_begin(int n_envs, hipStream_t st, const DevModel* m, const StepParams& P, const DevBuffers& B, unsigned char* need_reset);
 void launch_reward(int n_envs, hipStream_t st, const DevModel* m, const StepParams& P, const DevBuffers& B, float* reward);
 

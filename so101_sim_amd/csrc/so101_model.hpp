@@ -302,3 +302,8 @@ struct ContactOut {               // so101_contact_out: device pointers, any may
   int* pair_count;
   float *pair_dist, *pair_normal, *pair_force;
 };
+
+// ---- proximity sensing (so101_proximity.hpp): the outputs of one so101_proximity call
+struct ProxOut {                  // so101_proximity_out: device pointers, any may be NULL
+  float* dist; int* geom; float *point, *normal; int *flags, *queries;
+};

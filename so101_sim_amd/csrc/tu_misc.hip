@@ -1,7 +1,8 @@
-// Translation unit: physics-only stepping, the parity-test stage dump, contact sensing, reward, episode bookkeeping (Newton), the cameras, Cartesian tool control
+// Translation unit: physics-only stepping, the parity-test stage dump, contact sensing, proximity sensing, reward, episode bookkeeping (Newton), the cameras, Cartesian tool control
 // of both engines (the chain kernels for 6 columns - SO100 - and 8 - the general-tree engine, both builds).
 #include "so101_kernels.hpp"
 #include "so101_contacts.hpp"
+#include "so101_proximity.hpp"
 #include "so101_camera.hpp"
 #include "so101_tool_chain.hpp"
 #include "so101_launch.hpp"
@@ -44,6 +45,10 @@ void launch_contacts(int solver, int n, hipStream_t st, const DevModel* m, const
                      const TouchPairsT<4>& T, const ContactOut& O) {
   if (solver == 0) { launch_contacts_pgs(n, st, m, P, B, env_index, forces, T, O); return; }
   hipLaunchKernelGGL(k_contacts<1>, dim3((unsigned int)n), dim3(64), 0, st, m, P, B, env_index, forces, T, O);
+}
+void launch_proximity(int n, hipStream_t st, const DevModel* m, const StepParams& P, const DevBuffers& B, const int* env_index, const float* q,
+                      const TouchPairsT<4>& T, float max_dist, const ProxOut& O) {
+  hipLaunchKernelGGL(k_proximity, dim3((unsigned int)n * (unsigned int)T.npair), dim3(64), 0, st, m, P, B, env_index, q, T, max_dist, O);
 }
 void launch_begin(int n_envs, hipStream_t st, const DevModel* m, const StepParams& P, const DevBuffers& B, unsigned char* need_reset) {
   hipLaunchKernelGGL(k_begin, dim3(n_envs), dim3(64), 0, st, m, P, B, need_reset);

@@ -25,6 +25,7 @@ from ._dmenv import BoundedArray, Array, StepType, TimeStep
 from .calibration import SO101Calibration
 from .model import scenes
 from . import contacts as _contacts
+from . import proximity as _proximity
 from .tool_control import ToolControl
 
 DEFAULT_CONTROL_TIMESTEP = 0.02
@@ -118,7 +119,7 @@ class _PhysicsView:
         raise NotImplementedError("rendering is outside the MI355X hot path (SURVEY.md 8b)")
 
 
-class BatchedEnvironment(ToolControl, _contacts.ContactSensing):
+class BatchedEnvironment(ToolControl, _contacts.ContactSensing, _proximity.ProximitySensing):
     def __init__(self, task: SO100HandOverTask, n_envs: int = 1, time_limit: float = float("inf"),
                  random_state=None, device=None, env_id_base: int = 0, solver_iterations: int = 0,
                  solver_tolerance: float = -1.0, settle_max_substeps: int = 1000, solver: str = "newton",
@@ -465,6 +466,27 @@ class BatchedEnvironment(ToolControl, _contacts.ContactSensing):
         and the other in b), touching = count > 0, dist [n, npair] (the smallest, +inf without a contact) and, with forces=True,
         normal_force [n, npair] (sum of the normal forces) and force [n, npair, 3] (the net world-frame force ON group a), else None."""
         return self._touch(pairs, env_ids, forces)
+
+    # ------------------------------------------------------------------ proximity sensing (proximity.py: ProximitySensing)
+    def proximity(self, pairs, env_ids=None, q=None, max_dist: float = 0.1):
+        """How far apart: `pairs` is a sequence of 1 to 16 (a, b), each side anything geom_group() takes.  Per entry and pair, on the GPU
+        (so101_proximity), a proximity.ProximityReport of tensors on the env's device: dist [n, P], geom [n, P, 2] int32, point [n, P, 2, 3],
+        normal [n, P, 3], flags [n, P] int32.
+
+        Entries: the envs `env_ids` (None = all; an env may repeat).  With `q` [n, 6] - arm joint angles, the qpos[0:6] convention of
+        tool_pose(q=...) - entry i is evaluated with the props of env env_ids[i] where they are now and the arm at q[i]; env_ids = [e] * K
+        checks a K-waypoint trajectory against one env in one call.  Nothing bound is modified: qpos, qvel, ctrl and the warmstart stay.
+
+        Per entry and pair, over every geom pair (one geom in a, the other in b) the model's own pair list admits - the list the collision
+        stage walks, without same-body and excluded pairs, so "proximity < 0" and "touch" speak about the same pairs: `dist` is the smallest
+        signed distance.  Separated: the Euclidean gap of the two surfaces, >= 0.  Penetrating: the smallest contact dist of the narrowphase for
+        that geom pair (< 0, the number touch() gives), flags bit 1.  `geom`: the winning pair, the a-side geom first.  `point`: the closest
+        point on the a-side geom and on the b-side geom, world frame (penetrating: the contact position offset by -+ dist / 2 along the
+        normal).  `normal`: unit vector from the a point to the b point (penetrating: the contact normal, oriented from a to b).  Nothing
+        below `max_dist` (a finite number above 0, at most 10 m), or no admitted pair: dist = max_dist, geom -1, zeros, flags bit 4 - what
+        mj_geomDistance does with distmax.  flags bit 2: the distance iteration hit its cap on the winning pair, dist is an upper bound.
+        Ties go to the pair that comes first in the model's pair list."""
+        return self._proximity(pairs, env_ids, q, max_dist)
 
     def events(self, clear: bool = False) -> dict:
         """Counts since creation (or the last clear) of env-steps / env-resets that raised a flag: contact or candidate

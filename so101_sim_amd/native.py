@@ -32,7 +32,7 @@ EXPORTS = (
     "so101_version", "so101_max_contacts", "so101_create", "so101_destroy", "so101_default_config",
     "so101_configure", "so101_bind_state", "so101_bind_physics_state", "so101_set_reset_pool", "so101_compute_settled", "so101_set_settled_store", "so101_reset", "so101_settle", "so101_begin_episode", "so101_step", "so101_physics", "so101_reward",
     "so101_get_returns", "so101_get_diag", "so101_get_events", "so101_debug_forward", "so101_debug_candidates", "so101_debug_stages", "so101_get_info", "so101_debug_chain_stats", "so101_last_error",
-    "so101_set_hull_planes", "so101_render", "so101_ik_default_config", "so101_tool_pose", "so101_tool_ik", "so101_contacts",
+    "so101_set_hull_planes", "so101_render", "so101_ik_default_config", "so101_tool_pose", "so101_tool_ik", "so101_contacts", "so101_proximity",
     "so101_tree_create", "so101_tree_destroy", "so101_tree_dims", "so101_tree_last_plan", "so101_tree_bind_state", "so101_tree_configure", "so101_tree_physics",
     "so101_tree_debug_forward", "so101_tree_get_diag", "so101_tree_last_error", "so101_tree_obs_dim", "so101_tree_bind_env",
     "so101_tree_configure_env", "so101_tree_bind_physics_state", "so101_tree_reset", "so101_tree_step", "so101_tree_set_hull_planes", "so101_tree_render", "so101_tree_begin_episode", "so101_tree_settle", "so101_tree_compute_settled", "so101_tree_set_settled_store",
@@ -104,6 +104,14 @@ class ContactOut(C.Structure):
 class TreeGeomPair(C.Structure):
     """so101_tree_geom_pair of include/so101.h: two 256-bit geom masks"""
     _fields_ = [("a", C.c_uint32 * 8), ("b", C.c_uint32 * 8)]
+
+
+PROXIMITY_OUT_FIELDS = ("dist", "geom", "point", "normal", "flags", "queries")
+
+
+class ProximityOut(C.Structure):
+    """so101_proximity_out of include/so101.h: raw device addresses, None = not wanted"""
+    _fields_ = [(k, C.c_void_p) for k in PROXIMITY_OUT_FIELDS]
 
 
 def geom_pair_array(pairs, words: int = 4):
@@ -184,6 +192,7 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.so101_tool_pose.argtypes = [vp, C.POINTER(ToolSpec), vp, vp, C.c_int, vp, vp, vp, vp]
     L.so101_tool_ik.argtypes = [vp, C.POINTER(ToolSpec), C.POINTER(IkConfig), vp, vp, vp, vp, C.c_int, vp, vp, vp, vp]
     L.so101_contacts.argtypes = [vp, vp, C.c_int, C.c_int, C.POINTER(GeomPair), C.c_int, C.POINTER(ContactOut), vp]
+    L.so101_proximity.argtypes = [vp, vp, C.c_int, vp, C.POINTER(GeomPair), C.c_int, C.c_float, C.POINTER(ProximityOut), vp]
     _libs[path] = L
     return L
 
@@ -341,6 +350,11 @@ class Sim:
         """so101_contacts; pairs: sequence of (a words[4], b words[4]) geom masks; env_index and the fields of `out`: raw device addresses or None"""
         arr = geom_pair_array(pairs) if pairs else None
         self._check(self.L.so101_contacts(self.h, env_index, int(n), int(bool(forces)), arr, len(pairs) if pairs else 0, C.byref(out), stream), "so101_contacts")
+
+    def proximity(self, env_index, n: int, q, pairs, max_dist: float, out: ProximityOut, stream=0):
+        """so101_proximity; pairs: sequence of (a words[4], b words[4]) geom masks; env_index, q and the fields of `out`: raw device addresses or None"""
+        arr = geom_pair_array(pairs) if pairs else None
+        self._check(self.L.so101_proximity(self.h, env_index, int(n), q, arr, len(pairs) if pairs else 0, float(max_dist), C.byref(out), stream), "so101_proximity")
 
 
 class TreeConfig(C.Structure):
