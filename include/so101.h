@@ -35,7 +35,7 @@ extern "C" {
 
 #define SO101_ABI_VERSION 10     /* 10: so101_tree_last_plan, and (additions that change nothing older, so the number stays) the cameras: so101_camera,
                                     so101_set_hull_planes, so101_render, so101_tree_set_hull_planes, so101_tree_render, and Cartesian tool control: so101_tool, so101_ik_config, so101_ik_default_config,
-                                    so101_tool_pose, so101_tool_ik, proximity sensing: so101_proximity_out, so101_proximity, and the same (tool control) for the general-tree engine: so101_tree_tool, so101_tree_ik_config, so101_tree_tool_chain,
+                                    so101_tool_pose, so101_tool_ik, proximity sensing: so101_proximity_out, so101_proximity, so101_tree_proximity, and the same (tool control) for the general-tree engine: so101_tree_tool, so101_tree_ik_config, so101_tree_tool_chain,
                                     so101_tree_ik_default_config, so101_tree_tool_pose, so101_tree_tool_ik; 9: so101_tree_config gains the observation delays, so101_tree_bind_physics_state; 8: the general-tree engine (so101_tree_*) */
 #define SO101_OBS_DIM 18      /* joints_pos(6, delayed) | undelayed_joints_pos(6) | commanded_joints_pos(6) */
 #define SO101_ACT_DIM 6
@@ -399,7 +399,7 @@ int so101_contacts(so101_sim* sim, const int32_t* env_index, int n, int forces,
  * q: DEVICE [n][6] arm joint angles (qpos[0:6], the convention of so101_tool_pose) or NULL: entry i is evaluated with the props of env
  * env_index[i] where they are and the arm at q[i]; nothing bound is read for the arm's angles then and nothing bound is ever written - qpos, qvel,
  * ctrl and the warmstart stay as they are.  env_index may repeat an env: K waypoints against one env in one call.  An entry's output bits
- * depend on its env's state, q[i], its pair and max_dist only.  Asynchronous on `hip_stream`.  SO100 engine only; an addition: the ABI number stays.
+ * depend on its env's state, q[i], its pair and max_dist only.  Asynchronous on `hip_stream`.  This is the SO100 engine's; so101_tree_proximity below is the general-tree engine's.  An addition: the ABI number stays.
  *
  * env_index: DEVICE array of n env indices, or NULL for envs 0 .. n - 1.  pairs: HOST array of npair pairs, copied.  out: HOST struct of
  * DEVICE pointers.  SO101_ERR_ARG (with a message in so101_last_error): NULL handle or out; no output pointer at all; n outside 1 .. 2^26, or
@@ -584,6 +584,28 @@ typedef struct { uint32_t a[8], b[8]; } so101_tree_geom_pair;   /* 256-bit group
 int so101_tree_contacts(so101_tree* sim, const int32_t* env_index, int n, int forces,
                         const so101_tree_geom_pair* pairs /* HOST, npair of them */, int npair,
                         const so101_contact_out* out, void* hip_stream);
+
+/* ---- proximity sensing of this engine (k_tree_proximity of csrc/so101_tree_kernels.hpp): so101_proximity above on a tree handle, for both builds - the
+ * same semantics, conventions and flag meanings, the same distance code (csrc/so101_proximity_core.hpp), so101_proximity_out reused unchanged.  A group
+ * is a 256-bit mask over geoms (so101_tree_geom_pair).  The pass is load the env's state, the columns of q, kinematics; no dynamics runs.  A
+ * penetrating geom pair goes to this engine's narrowphase on geoms loaded as its collision stage loads them: its dist is so101_tree_contacts'
+ * pair_dist for that pair at that state, bit for bit, and flags bit 1 is set where that call reports a contact.
+ *
+ * q and q_adr: the arms are one-dof joints anywhere in qpos and a caller holds q in the column order of a tool's chain (what so101_tree_tool_ik
+ * returns), so q is DEVICE [n][ncol] with q_adr HOST [ncol], the qpos address of each column (so101_tree_tool_chain's qposadr, or any hinge /
+ * slide joint's), copied into the kernel arguments.  Entry i is evaluated with qpos[q_adr[k]] = q[i][k], k < ncol, and everything else - the other
+ * joints, the props - taken from env env_index[i].  Both NULL: the env's own qpos (ncol is ignored).  Joint equalities (the coupled fingers) are not
+ * enforced: the caller gives the configuration it means.  A NaN in q makes every geom it moves unreachable (flags 4 where only such geoms are
+ * asked for).  Nothing bound is ever written.  env_index may repeat an env: K waypoints against one env in one call.  An entry's output bits depend on
+ * its env's state, q[i], q_adr, its pair and max_dist only.  Asynchronous on `hip_stream`.  An addition: the ABI number stays.
+ *
+ * SO101_ERR_ARG with the messages of so101_proximity under the name so101_tree_proximity (ngeom is the handle's, dims[4]), and: q without q_adr or
+ * q_adr without q; ncol outside 1 .. 16; a q_adr entry that is not the qpos address of a hinge or slide joint; a repeated q_adr entry.
+ * SO101_ERR_STATE: no state bound. */
+int so101_tree_proximity(so101_tree* sim, const int32_t* env_index, int n, const float* q /* DEVICE [n][ncol] or NULL */,
+                         const int32_t* q_adr /* HOST [ncol] or NULL */, int ncol,
+                         const so101_tree_geom_pair* pairs /* HOST, npair of them */, int npair, float max_dist,
+                         const so101_proximity_out* out, void* hip_stream);
 const char* so101_tree_last_error(const so101_tree* sim);
 
 #ifdef __cplusplus

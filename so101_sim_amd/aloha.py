@@ -14,6 +14,8 @@ Cartesian tool control: `tool_pose`, `tool_chain`, `solve_ik` and `cartesian_act
 (tools.ALOHA_TOOLS) or any tools.Tool and the joint values that bring one to a target, batched on the GPU (so101_tree_tool_pose / so101_tree_tool_ik).
 Contact sensing: `contacts`, `touch` and `geom_group` give the contact list of the current state (64 contacts per env in the hand-over scenes, 160 in
 Dining) and "who touches whom" over pairs of geom groups (contacts.aloha_groups), batched on the GPU (so101_tree_contacts).
+Proximity sensing: `proximity` gives the smallest signed distance, the closest points and the normal over the same pairs of geom groups while they
+do not touch - per env, or per waypoint `q` of named joints (a tool's chain: what `solve_ik` returns) against an env's props (so101_tree_proximity).
 Not built: a non-default table height offset (the committed model blob is compiled for the reference's default).  The observation delays ARE parameters (`joints_observation_delay_secs`, `image_observation_delay_secs`,
 aloha2_task.py:153-159: whole control steps, handed to the kernels by so101_tree_configure_env), and `physics_state` /
 `delayed_physics_state` come from a device-side delay line (so101_tree_bind_physics_state).  Both reward modes are built: the overlap boxes (default) and the contact sequence
@@ -31,6 +33,7 @@ from ._dmenv import Array, BoundedArray, TimeStep
 from .model import blob as blobfmt
 from .model import scenes
 from . import contacts as _contacts
+from .proximity import ProximitySensing
 from .tool_control import ToolControl
 
 DEFAULT_CONTROL_TIMESTEP = 0.02
@@ -136,7 +139,7 @@ def aloha_action_spec(ctrlrange: np.ndarray, waist_joint_limit: float = np.pi / 
     return BoundedArray((14,), np.float32, lo, hi)
 
 
-class AlohaEnvironment(ToolControl, _contacts.ContactSensing):
+class AlohaEnvironment(ToolControl, _contacts.ContactSensing, ProximitySensing):
     def __init__(self, task: HandOverTask, n_envs: int = 1, time_limit: float = float("inf"), random_state=None, device=None,
                  env_id_base: int = 0, solver_iterations: int = 0, solver_tolerance: float = -1.0, settle_max_substeps: int = 1000,
                  physics_state: bool | None = None, seed_compatible: bool = True, narrowphase: str = "epa", prefetch_resets: bool = True, pipeline: bool = True):
@@ -567,6 +570,47 @@ class AlohaEnvironment(ToolControl, _contacts.ContactSensing):
         `("right_gripper", "object")`, `("left_gripper", "object")` and `("object", "container")` are the questions of the contact-sequence
         reward (hand_over.py:286-338), the last one that of the Dining `contact` reward."""
         return self._touch(pairs, env_ids, forces)
+
+    # ------------------------------------------------------------------ proximity sensing (proximity.py: ProximitySensing)
+    _q_is_columns = True
+
+    def _proximity_columns(self, joints):
+        """qpos addresses of q's columns: a tool's chain, explicit addresses, or (None) all one-dof joints in qpos order"""
+        from . import tools as _tools
+        if joints is None:
+            if getattr(self, "_onedof_qadr", None) is None:
+                m = blobfmt.unpack(self.task.load_blob("f32")[0])
+                jt, qadr = np.asarray(m["body_jnttype"]).ravel(), np.asarray(m["body_qposadr"]).ravel()
+                self._onedof_qadr = sorted(int(qadr[b]) for b in range(len(jt)) if int(jt[b]) in (native.TREE_JNT_HINGE, native.TREE_JNT_SLIDE))
+            return list(self._onedof_qadr)
+        if isinstance(joints, (str, _tools.Tool)):
+            return [int(a) for a in self.sim.tool_chain(self._resolve_tool(joints).body)[1]]
+        try:
+            adr = [int(a) for a in joints]
+        except (TypeError, ValueError):
+            raise ValueError(f"joints must be a tool, a tool name or a sequence of qpos addresses, got {joints!r}") from None
+        if not 1 <= len(adr) <= 16 or len(set(adr)) != len(adr):
+            raise ValueError(f"joints must name 1 .. 16 distinct qpos addresses, got {adr}")
+        return adr
+
+    def proximity(self, pairs, env_ids=None, q=None, joints=None, max_dist: float = 0.1):
+        """How far apart: `pairs` is a sequence of 1 to 16 (a, b), each side anything geom_group() takes.  Per entry and pair, on the GPU
+        (so101_tree_proximity), a proximity.ProximityReport of tensors on the env's device: dist [n, P], geom [n, P, 2] int32,
+        point [n, P, 2, 3], normal [n, P, 3], flags [n, P] int32 - the report, the conventions and the flag bits of
+        BatchedEnvironment.proximity (1 penetrating, 2 iteration cap, 4 nothing within max_dist, 8 env id out of range).
+
+        Entries: the envs `env_ids` (None = all; an env may repeat).  With `q` [n, ncol], entry i is evaluated with the joints `joints` at
+        q[i] and everything else - the other arm, the props - where env env_ids[i] has it; env_ids = [e] * K checks K waypoints against one
+        env in one call.  `joints`: a tool name or tools.Tool - q's columns are that tool's chain (tool_chain), so q is exactly what
+        solve_ik(tool=...) returned: 6 columns for a gripper, 7 for a finger; or a sequence of 1 .. 16 qpos addresses of hinge or slide
+        joints; or None: all one-dof joints in qpos order, q [n, 16].  Joint equalities (the coupled fingers) are not enforced: q is the
+        configuration the caller means.  A prop cannot be moved through q.  Nothing bound is modified.
+
+        `dist` is the smallest signed distance over the geom pairs (one geom in a, the other in b) the model's pair list admits - the list the
+        collision stage walks, so "proximity < 0" and touch() speak about the same pairs.  Separated: the Euclidean gap, >= 0.  Penetrating:
+        the smallest contact dist of the narrowphase for that geom pair, bit for bit touch()'s dist, flags bit 1.  Nothing below `max_dist`
+        (finite, above 0, at most 10 m): dist = max_dist, geom -1, zeros, flags bit 4."""
+        return self._proximity(pairs, env_ids, q, max_dist, joints=joints)
 
     def episode_returns(self):
         return self.ep_return

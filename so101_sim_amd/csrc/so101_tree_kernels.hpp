@@ -3,6 +3,7 @@
 // so101_tree_debug_forward layout (floats per env; dims[7..14] of so101_tree_dims report it): counts, bias, qacc_smooth, qacc [TV each],
 // body positions [TB][3], mass matrix [TV][TV], contacts [TCON][10] (pos3 normal3 dist geom1 geom2 dim), normal forces [TCON]
 #include "so101_contact_report.hpp"      // (guarded: the report tail of k_tree_contacts is one template for both builds)
+#include "so101_proximity_core.hpp"      // (guarded: the distance code of k_tree_proximity is the SO100 engine's)
 #undef TDBG_COUNTS
 #undef TDBG_BIAS
 #undef TDBG_QSM
@@ -506,5 +507,145 @@ __global__ void __launch_bounds__(64) k_tree_contacts(const TreeModel* tm, const
   }
   wave_sync();
   contact_report<TCON>(i, TreeContactView{L, G, ncon, L.flags, nkeep, forces && nrow > 0}, forces != 0, T, O);
+}
+
+// ---- proximity sensing (so101_tree_proximity of include/so101.h): k_proximity of the SO100 engine (so101_proximity.hpp) on this engine's state, one
+// wavefront per (entry, group pair); candidates, bounds, the exact query and the output record are so101_proximity_core.hpp's.  The pass is
+// load_state, the columns of `q` (qpos[C.adr[k]] = q[i][k]: the addresses are kernel arguments, picked by a select over the lane index), kinematics.
+// No dynamics runs and nothing is stored to a bound buffer.
+//   * Bounding spheres of all geoms go into L.aabb (TGEOM columns), from the pose load_geom_at() gives with the body's xpos / xmat, as collision()
+//     and k_tree_render_frames take it (this engine's geom_dyn is the body id).
+//   * Groups are 256-bit masks held in eight registers each; membership is a select over the eight words, not an indexed array.
+//   * The candidate list (pair word, bound) lives in the contact slots L.con, PROX_ROUND pairs per round: in the 32-dof build 64 contacts x 128 B is
+//     exactly 2 x 1024 words.  The Dining scenes' 23 016 pairs are 23 rounds; the pair words are read four blocks of 64 in flight, the way
+//     tree::broadphase reads them (one block per trip paid a round trip to the pair list each), and the ballots run block by block, so the list
+//     stays in pair order.
+//   * Members are appended in pair order, the smallest bound goes first, the walk stops when no bound is below the best, ties go to the earlier
+//     pair, "geom1 in a" is tried before the swapped order: k_proximity's rules.
+//   * A separated pair is the shared GJK with NoCache (hulls here go up to 5 676 vertices).  A pair whose simplex holds the origin or whose gap is
+//     below PROX_HANDOVER goes to narrow_pair<HullCache, G64> on geoms loaded exactly as tree::collision() loads them: the reported distance is
+//     what so101_tree_contacts reports as pair_dist, bit for bit.
+static_assert(2 * PROX_ROUND * 4 <= sizeof(((TreeLDS*)0)->con), "the candidate list must fit the contact slots");
+static_assert(PROX_ROUND % (4 * WAVE) == 0, "a round is a whole number of trips of four blocks");
+
+// bit g of a 256-bit group mask held in eight registers (selects with constant indices: no scratch memory)
+DEV bool tree_prox_member(unsigned int w0, unsigned int w1, unsigned int w2, unsigned int w3, unsigned int w4, unsigned int w5, unsigned int w6, unsigned int w7, int g) {
+  const int k = (g >> 5) & 7;
+  const unsigned int lo = k == 0 ? w0 : k == 1 ? w1 : k == 2 ? w2 : w3, hi = k == 4 ? w4 : k == 5 ? w5 : k == 6 ? w6 : w7;
+  return (((k < 4 ? lo : hi) >> (g & 31)) & 1u) != 0u;
+}
+
+__global__ void __launch_bounds__(64) k_tree_proximity(const TreeModel* tm, const DevModel* gm, TreeBuffers B, int N, const int* env_index, const float* q, ProxCols C,
+                                                       TouchPairsT<8> T, float max_dist, ProxOut O) {
+  BLOCK_SHARED(TreeLDS, L);
+  const int lane = wave_lane();
+  const unsigned int npair_q = (unsigned int)T.npair;
+  const size_t i = blockIdx.x / npair_q;
+  const int p = wave_uniform_i((int)(blockIdx.x - (unsigned int)i * npair_q));
+  const size_t o = (size_t)blockIdx.x;
+  const int e = env_index ? wave_uniform_i(env_index[i]) : (int)i;
+  const float zero[3] = {0.f, 0.f, 0.f};
+  if (e < 0 || e >= N) { prox_store(o, max_dist, false, -1, -1, zero, zero, zero, max_dist, PROX_FLAG_OUTSIDE, 0, O); return; }
+  tree::load_state(tm, L, B, e, N);
+  if (q) {
+    int adr = 0;
+#pragma unroll
+    for (int k = 0; k < PROX_MAXCOL; k++) adr = lane == k ? C.adr[k] : adr;
+    if (lane < C.ncol) L.qpos[adr] = q[i * (size_t)C.ncol + lane];
+    wave_sync();
+  }
+  tree::kinematics(tm, L);
+  // bounding spheres: rows 0-2 the centre, row 3 the radius; a plane keeps its point in rows 0-2 and its normal in rows 3-5 (prox_bound)
+  const int ngeom = ldc(&gm->ngeom);
+  for (int g = lane; g < ngeom && g < TGEOM; g += WAVE) {
+    int b = gm->geom_dyn[g];
+    b = b < 0 ? 0 : b;
+    GeomW G;
+    load_geom_at<G16>(gm, g, L.xpos[b], L.xmat[b], G);
+    const bool plane = G.type == G_PLANE;
+#pragma unroll
+    for (int k = 0; k < 3; k++) L.aabb[k][g] = plane ? G.p[k] : G.c[k];
+    L.aabb[3][g] = plane ? G.R[2] : gm->geom_rbound[g];
+    L.aabb[4][g] = plane ? G.R[5] : 0.f;
+    L.aabb[5][g] = plane ? G.R[8] : 0.f;
+  }
+  wave_sync();
+  const unsigned int a0 = T.a[p][0], a1 = T.a[p][1], a2 = T.a[p][2], a3 = T.a[p][3], a4 = T.a[p][4], a5 = T.a[p][5], a6 = T.a[p][6], a7 = T.a[p][7];
+  const unsigned int b0 = T.b[p][0], b1 = T.b[p][1], b2 = T.b[p][2], b3 = T.b[p][3], b4 = T.b[p][4], b5 = T.b[p][5], b6 = T.b[p][6], b7 = T.b[p][7];
+  unsigned int* cword = (unsigned int*)&L.con[0];
+  float* cbound = (float*)&L.con[0] + PROX_ROUND;
+  const unsigned int* pairs = ldc(&gm->pair_packed);
+  const int npair = ldc(&gm->npair);
+  float best = max_dist;
+  bool found = false;
+  int bg1 = -1, bg2 = -1, bflags = 0, bswap = 0, bround = 0, bidx = 0, queries = 0;
+  float bpa[3] = {0.f, 0.f, 0.f}, bpb[3] = {0.f, 0.f, 0.f}, bn[3] = {0.f, 0.f, 0.f};
+#pragma unroll 1
+  for (int c0 = 0; c0 < npair; c0 += PROX_ROUND) {
+    // ---- the round's members and their bounds, appended in pair order
+    int ncand = 0;
+    wave_sync();                                         // (the previous round's list has been read)
+#pragma unroll 1
+    for (int j0 = 0; j0 < PROX_ROUND; j0 += 4 * WAVE) {
+      if (c0 + j0 >= npair) break;
+      unsigned int pk[4];
+#pragma unroll
+      for (int u = 0; u < 4; u++) { const int pi = c0 + j0 + u * WAVE + lane; pk[u] = pi < npair ? pairs[pi] : 0xffffffffu; }
+      bool member[4], swapped[4];
+      float lb[4];
+#pragma unroll
+      for (int u = 0; u < 4; u++) {
+        const unsigned int w = pk[u];
+        const bool valid = w != 0xffffffffu;
+        int g1 = valid ? (int)(w & 0xffu) : 0, g2 = valid ? (int)((w >> 8) & 0xffu) : 0;
+        g1 = g1 < TGEOM ? g1 : 0; g2 = g2 < TGEOM ? g2 : 0;
+        const bool ab = tree_prox_member(a0, a1, a2, a3, a4, a5, a6, a7, g1) && tree_prox_member(b0, b1, b2, b3, b4, b5, b6, b7, g2);
+        const bool ba = !ab && tree_prox_member(a0, a1, a2, a3, a4, a5, a6, a7, g2) && tree_prox_member(b0, b1, b2, b3, b4, b5, b6, b7, g1);
+        lb[u] = prox_bound(L, w, g1, g2);
+        member[u] = valid && (ab || ba) && lb[u] < max_dist;          // (a NaN bound: not a member)
+        swapped[u] = ba;
+      }
+#pragma unroll
+      for (int u = 0; u < 4; u++) {
+        const unsigned long long mask = wave_ballot(member[u]);
+        const int idx = ncand + wave_prefix(mask);
+        if (member[u]) { cword[idx] = (pk[u] & 0x1ffffu) | (swapped[u] ? 0x20000u : 0u); cbound[idx] = lb[u]; }
+        ncand += __popcll(mask);
+      }
+    }
+    wave_sync();
+    // ---- smallest bound first, until no bound is below the best
+#pragma unroll 1
+    for (int t = 0; t < PROX_ROUND; t++) {
+      float val = -3.0e38f; int idx = 0x7fffffff;
+      for (int k = lane; k < ncand; k += WAVE) { const float b = -cbound[k]; if (b > val) { val = b; idx = k; } }
+      wave_argmax(val, idx);
+      const float lbmin = -val;
+      if (idx < 0 || idx >= ncand || !(lbmin <= best) || !(lbmin < max_dist)) break;
+      const unsigned int w = cword[idx];
+      wave_sync();
+      if (lane == 0) cbound[idx] = 3.0e38f;
+      wave_sync();
+      const int g1 = wave_uniform_i((int)(w & 0xffu)), g2 = wave_uniform_i((int)((w >> 8) & 0xffu));
+      const int bd1 = wave_uniform_i(tm->geom_body[g1]), bd2 = wave_uniform_i(tm->geom_body[g2]);
+      GeomW G1, G2;
+      load_geom_at(gm, g1, L.xpos[bd1], L.xmat[bd1], G1); load_geom_at(gm, g2, L.xpos[bd2], L.xmat[bd2], G2);
+      ProxResult R;
+      queries++;
+      if (!prox_pair_geoms<HullCache, G64>(gm, G1, G2, g1, g2, best, R)) continue;
+      // ties go to the earlier pair: within a round the list is in pair order, rounds come in pair order
+      const bool better = R.dist < best || (found && R.dist == best && c0 == bround && idx < bidx);
+      if (R.dist < max_dist && better) {
+        best = R.dist; found = true; bg1 = g1; bg2 = g2; bflags = R.flags; bswap = (int)((w >> 17) & 1u); bround = c0; bidx = idx;
+#pragma unroll
+        for (int k = 0; k < 3; k++) { bpa[k] = R.pa[k]; bpb[k] = R.pb[k]; bn[k] = R.n[k]; }
+      }
+    }
+  }
+  // the a-side geom first: a member in the second order is reported swapped, its normal negated
+  const bool sw = bswap != 0;
+  const float na[3] = {sw ? -bn[0] : bn[0], sw ? -bn[1] : bn[1], sw ? -bn[2] : bn[2]};
+  const float qa[3] = {sw ? bpb[0] : bpa[0], sw ? bpb[1] : bpa[1], sw ? bpb[2] : bpa[2]}, qb[3] = {sw ? bpa[0] : bpb[0], sw ? bpa[1] : bpb[1], sw ? bpa[2] : bpb[2]};
+  prox_store(o, max_dist, found, sw ? bg2 : bg1, sw ? bg1 : bg2, qa, qb, na, best, bflags, queries, O);
 }
 }  // namespace TREE_NS

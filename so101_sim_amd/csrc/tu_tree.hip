@@ -368,6 +368,52 @@ int TAPI(contacts)(TreeHandle* s, const int32_t* env_index, int n, int forces, c
   return SO101_OK;
 }
 
+// ---- proximity sensing (k_tree_proximity of so101_tree_kernels.hpp; the checks of so101_proximity in its order, then the columns of q)
+int TAPI(proximity)(TreeHandle* s, const int32_t* env_index, int n, const float* q, const int32_t* q_adr, int ncol, const so101_tree_geom_pair* pairs, int npair, float max_dist,
+                    const so101_proximity_out* out, void* stream) {
+  if (!s) return SO101_ERR_ARG;
+  const so101_proximity_out* o = out;
+  const char* bad = nullptr;
+  if (!o) bad = "NULL out";
+  else if (!o->dist && !o->geom && !o->point && !o->normal && !o->flags && !o->queries) bad = "no output (every pointer of out is NULL)";
+  else if (n < 1 || n > (1 << 26)) bad = "n must be 1 .. 2^26";
+  else if (!env_index && n > s->n_envs) bad = "n exceeds the envs of the handle";
+  else if (npair < 1 || npair > SO101_TOUCH_MAX_PAIRS) bad = "npair must be 1 .. 16";
+  else if (!pairs) bad = "NULL pairs";
+  if (bad) { s->err = std::string("so101_tree_proximity: ") + bad; return SO101_ERR_ARG; }
+  TouchPairsT<8> T{};
+  if (int rc = pack_touch_pairs(s, "so101_tree_proximity", pairs, npair, s->hm.ngeom, T)) return rc;
+  if (!(std::isfinite(max_dist) && max_dist > 0.f && max_dist <= 10.f)) { s->err = "so101_tree_proximity: max_dist must be a finite number above 0 and at most 10"; return SO101_ERR_ARG; }
+  ProxCols C{};
+  if (q && !q_adr) bad = "q without q_adr";
+  else if (!q && q_adr) bad = "q_adr without q";
+  else if (q && (ncol < 1 || ncol > PROX_MAXCOL)) bad = "ncol must be 1 .. 16";
+  if (bad) { s->err = std::string("so101_tree_proximity: ") + bad; return SO101_ERR_ARG; }
+  if (q) {
+    C.ncol = ncol;
+    for (int k = 0; k < ncol; k++) {
+      bool joint = false;
+      for (int b = 1; b < s->hm.nbody; b++)
+        joint = joint || ((s->hm.body_jnttype[b] == TJ_HINGE || s->hm.body_jnttype[b] == TJ_SLIDE) && s->hm.body_qposadr[b] == q_adr[k]);
+      if (!joint) {
+        s->err = "so101_tree_proximity: q_adr[" + std::to_string(k) + "] = " + std::to_string(q_adr[k]) + " is not the qpos address of a hinge or slide joint";
+        return SO101_ERR_ARG;
+      }
+      for (int j = 0; j < k; j++)
+        if (q_adr[j] == q_adr[k]) {
+          s->err = "so101_tree_proximity: q_adr[" + std::to_string(k) + "] repeats address " + std::to_string(q_adr[k]) + " of q_adr[" + std::to_string(j) + "]";
+          return SO101_ERR_ARG;
+        }
+      C.adr[k] = q_adr[k];
+    }
+  }
+  if (!s->bound) { s->err = "so101_tree_proximity: state buffers not bound (call so101_tree_bind_state)"; return SO101_ERR_STATE; }
+  GUARD_DEVICE(s);
+  hipLaunchKernelGGL(k_tree_proximity, dim3((unsigned int)n * (unsigned int)npair), dim3(64), 0, (hipStream_t)stream, s->dm, s->dg, s->buf, s->n_envs, (const int*)env_index, q, C, T,
+                     max_dist, ProxOut{o->dist, (int*)o->geom, o->point, o->normal, (int*)o->flags, (int*)o->queries});
+  return hip_ok(s, hipGetLastError(), "k_tree_proximity") ? SO101_OK : SO101_ERR_HIP;
+}
+
 int TAPI(get_diag)(TreeHandle* s, int* out /* [n_envs][8] device or host-visible memory */, void* stream) {
   if (!s || !out) return SO101_ERR_ARG;
   GUARD_DEVICE(s);

@@ -35,7 +35,8 @@
   int so101_tree##V##_tool_pose(void*, const so101_tree_tool*, const float*, const int32_t*, int, float*, float*, float*, void*);              \
   int so101_tree##V##_tool_ik(void*, const so101_tree_tool*, const so101_tree_ik_config*, const float*, const float*, const float*, const int32_t*, int, float*, float*, \
                               int32_t*, void*);                                                                                                \
-  int so101_tree##V##_contacts(void*, const int32_t*, int, int, const so101_tree_geom_pair*, int, const so101_contact_out*, void*);
+  int so101_tree##V##_contacts(void*, const int32_t*, int, int, const so101_tree_geom_pair*, int, const so101_contact_out*, void*);         \
+  int so101_tree##V##_proximity(void*, const int32_t*, int, const float*, const int32_t*, int, const so101_tree_geom_pair*, int, float, const so101_proximity_out*, void*);
 
 // (the builds define these with their own handle type in place of void*: same C symbol, same calling convention)
 extern "C" {
@@ -122,6 +123,10 @@ int so101_tree_tool_ik(so101_tree* s, const so101_tree_tool* tool, const so101_t
 }
 int so101_tree_contacts(so101_tree* s, const int32_t* env_index, int n, int forces, const so101_tree_geom_pair* pairs, int npair, const so101_contact_out* out, void* stream) {
   return s ? FWD(contacts, env_index, n, forces, pairs, npair, out, stream) : SO101_ERR_ARG;
+}
+int so101_tree_proximity(so101_tree* s, const int32_t* env_index, int n, const float* q, const int32_t* q_adr, int ncol, const so101_tree_geom_pair* pairs, int npair, float max_dist,
+                         const so101_proximity_out* out, void* stream) {
+  return s ? FWD(proximity, env_index, n, q, q_adr, ncol, pairs, npair, max_dist, out, stream) : SO101_ERR_ARG;
 }
 
 }  // extern "C"

@@ -36,7 +36,7 @@ EXPORTS = (
     "so101_tree_create", "so101_tree_destroy", "so101_tree_dims", "so101_tree_last_plan", "so101_tree_bind_state", "so101_tree_configure", "so101_tree_physics",
     "so101_tree_debug_forward", "so101_tree_get_diag", "so101_tree_last_error", "so101_tree_obs_dim", "so101_tree_bind_env",
     "so101_tree_configure_env", "so101_tree_bind_physics_state", "so101_tree_reset", "so101_tree_step", "so101_tree_set_hull_planes", "so101_tree_render", "so101_tree_begin_episode", "so101_tree_settle", "so101_tree_compute_settled", "so101_tree_set_settled_store",
-    "so101_tree_tool_chain", "so101_tree_ik_default_config", "so101_tree_tool_pose", "so101_tree_tool_ik", "so101_tree_contacts",
+    "so101_tree_tool_chain", "so101_tree_ik_default_config", "so101_tree_tool_pose", "so101_tree_tool_ik", "so101_tree_contacts", "so101_tree_proximity",
 )
 
 
@@ -403,6 +403,7 @@ class TreeSim:
         L.so101_tree_tool_pose.argtypes = [vp, C.POINTER(ToolSpec), vp, vp, C.c_int, vp, vp, vp, vp]
         L.so101_tree_tool_ik.argtypes = [vp, C.POINTER(ToolSpec), C.POINTER(TreeIkConfig), vp, vp, vp, vp, C.c_int, vp, vp, vp, vp]
         L.so101_tree_contacts.argtypes = [vp, vp, C.c_int, C.c_int, C.POINTER(TreeGeomPair), C.c_int, C.POINTER(ContactOut), vp]
+        L.so101_tree_proximity.argtypes = [vp, vp, C.c_int, vp, C.POINTER(C.c_int32), C.c_int, C.POINTER(TreeGeomPair), C.c_int, C.c_float, C.POINTER(ProximityOut), vp]
         self.n_envs = int(n_envs)
         h = C.c_void_p()
         rc = L.so101_tree_create(blob_f32, len(blob_f32), self.n_envs, int(device), C.byref(h))
@@ -543,3 +544,11 @@ class TreeSim:
         None.  The per-contact fields of `out` have max_contacts slots per entry."""
         arr = geom_pair_array(pairs, 8) if pairs else None
         self._check(self.L.so101_tree_contacts(self.h, env_index, int(n), int(bool(forces)), arr, len(pairs) if pairs else 0, C.byref(out), stream), "so101_tree_contacts")
+
+    def proximity(self, env_index, n: int, q, q_adr, pairs, max_dist: float, out: ProximityOut, stream=0):
+        """so101_tree_proximity; pairs: sequence of (a words[8], b words[8]) geom masks; q_adr: the qpos addresses of q's columns (a sequence of
+        ints, host side) or None; env_index, q [n][len(q_adr)] and the fields of `out`: raw device addresses or None"""
+        arr = geom_pair_array(pairs, 8) if pairs else None
+        adr = (C.c_int32 * len(q_adr))(*[int(a) for a in q_adr]) if q_adr is not None and len(q_adr) else None
+        self._check(self.L.so101_tree_proximity(self.h, env_index, int(n), q, adr, len(q_adr) if q_adr is not None else 0, arr, len(pairs) if pairs else 0, float(max_dist),
+                                                C.byref(out), stream), "so101_tree_proximity")

@@ -4,8 +4,13 @@ MuJoCo answers "how far apart are these two things" with `mj_geomDistance` or a 
 Here the question is asked per env (or per arm waypoint against an env's props) and pair of geom groups on the GPU: the smallest signed
 distance over the geom pairs the model's own pair list admits, with the closest points.  The groups are those of contacts.py.
 
-Limits: the SO100 engine only; distances are reported below `max_dist` (at most 10 m); a penetrating pair reports the narrowphase's contact
-distance, the number `touch` gives at the same state."""
+Both engines answer it: `BatchedEnvironment.proximity` (SO100, `so101_proximity`: 128-bit groups, `q` the six arm joints) and
+`AlohaEnvironment.proximity` (the ALOHA hand-over and Dining scenes, `so101_tree_proximity`: 256-bit groups, `q` as columns of named joints -
+a tool's chain, what `solve_ik` returns, or any one-dof joints by qpos address).  One distance code runs under both
+(csrc/so101_proximity_core.hpp).
+
+Limits: distances are reported below `max_dist` (at most 10 m); a penetrating pair reports the narrowphase's contact distance, the number
+`touch` gives at the same state; `q` places arm joints only, never a prop; joint equalities are not enforced on `q`."""
 from __future__ import annotations
 
 import collections
@@ -54,9 +59,18 @@ def records(report: ProximityReport, entry: int = 0) -> list:
 class ProximitySensing:
     """Proximity sensing of a batched environment, on the pattern of contacts.ContactSensing: output allocation and argument handling of
     `proximity`.  The environment supplies `geom_group` and `_geom_limit` (ContactSensing), `_env_index` and `_joint_rows` (ToolControl), and keeps
-    its own public `proximity` with its documentation; `self.sim` has proximity (native.Sim)."""
+    its own public `proximity` with its documentation; `self.sim` has proximity (native.Sim, native.TreeSim).  An environment whose `q` is a
+    set of joint columns (the general-tree engine) overrides `_proximity_columns`."""
 
-    def _proximity(self, pairs, env_ids, q, max_dist, queries=False):
+    _q_is_columns = False          # True: sim.proximity takes the qpos addresses of q's columns after q (native.TreeSim)
+
+    def _proximity_columns(self, joints):
+        """the qpos addresses of q's columns, or None where q is the engine's fixed arm (SO100: qpos[0:6])"""
+        if joints is not None:
+            raise ValueError("joints: this engine's q is the six arm joints, qpos[0:6]")
+        return None
+
+    def _proximity(self, pairs, env_ids, q, max_dist, queries=False, joints=None):
         from . import native
         pairs = list(pairs)
         if not 1 <= len(pairs) <= MAX_PAIRS:
@@ -71,14 +85,20 @@ class ProximitySensing:
         masks = [(self.geom_group(a).mask(words), self.geom_group(b).mask(words)) for a, b in pairs]
         torch = self.torch
         idx, n = self._env_index(env_ids)
+        if q is None and joints is not None:
+            raise ValueError("joints names the columns of q: it needs q")
+        adr = self._proximity_columns(joints) if q is not None else None
         if q is not None:
-            q = self._joint_rows(q, 6, "q")
+            ncol = 6 if adr is None else len(adr)
+            what = "arm joint angles" if adr is None else "joint values"
+            q = self._joint_rows(q, ncol, "q")
             if q.shape[0] != n:
-                raise ValueError(f"q must be [{n}, 6]: one row of arm joint angles per entry, got {tuple(q.shape)}")
+                raise ValueError(f"q must be [{n}, {ncol}]: one row of {what} per entry, got {tuple(q.shape)}")
         P = len(masks)
         e = lambda *s, dt=torch.float32: torch.empty(*s, dtype=dt, device=self.device)
         rep = ProximityReport(e(n, P), e(n, P, 2, dt=torch.int32), e(n, P, 2, 3), e(n, P, 3), e(n, P, dt=torch.int32))
         count = e(n, P, dt=torch.int32) if queries else None
         out = native.ProximityOut(queries=count.data_ptr() if queries else None, **{k: t.data_ptr() for k, t in rep._asdict().items()})
-        self.sim.proximity(idx.data_ptr() if idx is not None else None, n, q.data_ptr() if q is not None else None, masks, max_dist, out, self._stream())
+        columns = (adr,) if self._q_is_columns else ()          # (the general-tree engine's call takes the addresses after q)
+        self.sim.proximity(idx.data_ptr() if idx is not None else None, n, q.data_ptr() if q is not None else None, *columns, masks, max_dist, out, self._stream())
         return (rep, count) if queries else rep
