@@ -34,7 +34,7 @@ extern "C" {
 #endif
 
 #define SO101_ABI_VERSION 10     /* 10: so101_tree_last_plan, and (additions that change nothing older, so the number stays) the cameras: so101_camera,
-                                    so101_set_hull_planes, so101_render, so101_tree_set_hull_planes, so101_tree_render, and Cartesian tool control: so101_tool, so101_ik_config, so101_ik_default_config,
+                                    so101_set_hull_planes, so101_render, so101_tree_set_hull_planes, so101_tree_render, the colour cameras: so101_shading, so101_color_out, so101_render_color, so101_tree_render_color, and Cartesian tool control: so101_tool, so101_ik_config, so101_ik_default_config,
                                     so101_tool_pose, so101_tool_ik, proximity sensing: so101_proximity_out, so101_proximity, so101_tree_proximity, and the same (tool control) for the general-tree engine: so101_tree_tool, so101_tree_ik_config, so101_tree_tool_chain,
                                     so101_tree_ik_default_config, so101_tree_tool_pose, so101_tree_tool_ik; 9: so101_tree_config gains the observation delays, so101_tree_bind_physics_state; 8: the general-tree engine (so101_tree_*) */
 #define SO101_OBS_DIM 18      /* joints_pos(6, delayed) | undelayed_joints_pos(6) | commanded_joints_pos(6) */
@@ -283,6 +283,40 @@ typedef struct {
 int so101_render(so101_sim* sim, const so101_camera* cams, int ncam, int height, int width, const int32_t* env_index, int n_render,
                  float* depth, int32_t* seg, void* hip_stream);
 
+/* ---- colour cameras (csrc/so101_shade.hpp): so101_render with two more outputs per pixel - the world-frame unit normal of the surface the ray
+ * hit and a Lambert-shaded flat colour.  What is drawn is the COLLISION geometry of so101_render, one colour per geom, lit by directional lights:
+ * this is not MuJoCo's renderer - no textures, shadows, specular term, visual-only meshes or positional lights.  Stands in for the RGB image of
+ * physics.render(camera_id=...) that the reference's observation.images.<camera> carry (scripts/so101_lerobot_wrapper.py:85-98).
+ *
+ * Pixel: ray, hit, depth and seg are so101_render's, bit for bit.  normal: the outward normal of the feature through which the ray enters the hit
+ * geom, geom frame, rotated by the geom's world matrix, unit - plane +z; sphere x / |x| at the hit point x; capsule x minus its projection onto the
+ * axis segment, normalised; cylinder the side (radial) if the side's entry parameter is >= the slab's, else the cap (0, 0, -sign(d.z)); box the axis
+ * whose slab entry parameter is largest (x before y before z at equal values), -sign(d[axis]) along it; mesh the hull plane with the largest
+ * t = -num / den among planes with den < 0 (the first in plane order at equal t); no hit: 0.  rgb: v_k = clamp(C_g[k] (ambient[k] +
+ * sum_l diffuse_l[k] max(0, -n . u_l)), 0, 1), byte (uint8)(255 v_k + 0.5), C_g the colour of the hit geom, u_l the unit world direction light l
+ * travels (`dir`; for a light flagged `headlight` the camera's viewing direction, `dir` unread); no hit: `background`, converted the same way.
+ * A pixel's bits depend on the env's qpos, the camera, (r, c, height, width), that env's colours and the shading only.
+ *
+ * geom_rgb: DEVICE [ngeom][3], or [n_envs][ngeom][3] with rgb_per_env != 0 (entry i uses the row of env env_index[i]); caller-owned, values are
+ * clamped by the formula, not checked.  out: HOST struct of DEVICE pointers.  Asynchronous on `hip_stream`, changes no state.  Errors: those of
+ * so101_render for the shared arguments, and SO101_ERR_ARG (with a message) for NULL shading, geom_rgb or out; no output pointer at all; nlight
+ * outside 0 .. SO101_MAX_LIGHTS; a non-headlight dir whose length is not within 1e-4 of 1; a non-finite or negative ambient, diffuse or
+ * background. */
+#define SO101_MAX_LIGHTS 4
+typedef struct {
+  float ambient[3], background[3];
+  int32_t nlight;                                   /* 0 .. SO101_MAX_LIGHTS */
+  struct { float dir[3]; float diffuse[3]; int32_t headlight; } light[SO101_MAX_LIGHTS];
+} so101_shading;                                    /* HOST, copied */
+typedef struct {
+  uint8_t* rgb;      /* [n_render][ncam][height][width][3] */
+  float*   normal;   /* [n_render][ncam][height][width][3] */
+  float*   depth;    /* as so101_render */
+  int32_t* seg;      /* as so101_render */
+} so101_color_out;                                  /* DEVICE pointers, any may be NULL, not all */
+int so101_render_color(so101_sim* sim, const so101_camera* cams, int ncam, int height, int width, const int32_t* env_index, int n_render,
+                       const so101_shading* shading, const float* geom_rgb, int rgb_per_env, const so101_color_out* out, void* hip_stream);
+
 /* ---- Cartesian tool control (csrc/so101_tool_chain.hpp): the pose and Jacobian of a frame fixed to an arm link, and the inverse map, for thousands of
  * envs per call on the device.  so101_tool_pose stands in for physics.named.data.site_xpos / site_xmat and mujoco.mj_jacSite of the reference;
  * so101_tool_ik for dm_control's qpos_from_site_pose (dm_control/utils/inverse_kinematics.py), which the reference's data generator approximates by
@@ -520,6 +554,11 @@ int so101_tree_step(so101_tree* sim, const float* action /*[n_envs][nu]*/, float
 int so101_tree_set_hull_planes(so101_tree* sim, const float* planes, const int32_t* plane_adr);
 int so101_tree_render(so101_tree* sim, const so101_camera* cams, int ncam, int height, int width, const int32_t* env_index, int n_render,
                       int source, float* depth, int32_t* seg, void* hip_stream);
+/* ---- colour cameras of this engine: so101_render_color above, word for word, on a tree handle (`source` as in so101_tree_render; geom_rgb rows
+ * have the handle's ngeom, dims[4]); the error messages carry the name so101_tree_render_color. */
+int so101_tree_render_color(so101_tree* sim, const so101_camera* cams, int ncam, int height, int width, const int32_t* env_index, int n_render,
+                            int source, const so101_shading* shading, const float* geom_rgb, int rgb_per_env, const so101_color_out* out,
+                            void* hip_stream);
 /* ---- Cartesian tool control of this engine (csrc/so101_tool_chain.hpp): so101_tool_pose / so101_tool_ik above for a frame on any articulated body of
  * a general-tree model - the grippers and fingers of the two ALOHA arms (the sites left/gripper, right/gripper and the four finger sites of
  * aloha_pbr.xml), on both builds of the engine.  The chain of a tool is the bodies between the world and the tool's body that carry a hinge or slide

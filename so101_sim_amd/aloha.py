@@ -9,7 +9,10 @@ array container.  n_envs == 1 yields numpy observations without the env dimensio
 torch tensors on the GPU with a leading env dimension.
 
 Cameras: `render_depth` casts the scene's six cameras (cameras.ALOHA_CAMERAS) or any cameras.Camera against the collision geometry
-on the GPU (so101_tree_render) - depth and geom ids, from the current or the delayed state; not RGB, and not wired into the observation.
+on the GPU (so101_tree_render) - depth and geom ids, from the current or the delayed state; not wired into the observation.
+`render_color` (so101_tree_render_color, appearance.py) adds a colour image and surface normals of the same collision geometry,
+flat-coloured per geom and Lambert-shaded by directional lights - not MuJoCo's renderer: no textures, shadows, specular term,
+visual-only meshes or positional lights.
 Cartesian tool control: `tool_pose`, `tool_chain`, `solve_ik` and `cartesian_action` give the pose and Jacobian of the six tool sites
 (tools.ALOHA_TOOLS) or any tools.Tool and the joint values that bring one to a target, batched on the GPU (so101_tree_tool_pose / so101_tree_tool_ik).
 Contact sensing: `contacts`, `touch` and `geom_group` give the contact list of the current state (64 contacts per env in the hand-over scenes, 160 in
@@ -32,6 +35,7 @@ from . import native
 from ._dmenv import Array, BoundedArray, TimeStep
 from .model import blob as blobfmt
 from .model import scenes
+from . import appearance as _appearance
 from . import contacts as _contacts
 from .proximity import ProximitySensing
 from .tool_control import ToolControl
@@ -139,7 +143,7 @@ def aloha_action_spec(ctrlrange: np.ndarray, waist_joint_limit: float = np.pi / 
     return BoundedArray((14,), np.float32, lo, hi)
 
 
-class AlohaEnvironment(ToolControl, _contacts.ContactSensing, ProximitySensing):
+class AlohaEnvironment(ToolControl, _contacts.ContactSensing, ProximitySensing, _appearance.ColorCameras):
     def __init__(self, task: HandOverTask, n_envs: int = 1, time_limit: float = float("inf"), random_state=None, device=None,
                  env_id_base: int = 0, solver_iterations: int = 0, solver_tolerance: float = -1.0, settle_max_substeps: int = 1000,
                  physics_state: bool | None = None, seed_compatible: bool = True, narrowphase: str = "epa", prefetch_resets: bool = True, pipeline: bool = True):
@@ -450,6 +454,30 @@ class AlohaEnvironment(ToolControl, _contacts.ContactSensing, ProximitySensing):
         self.sim.render([c.spec() for c in cams], height, width, idx.data_ptr() if idx is not None else None, n,
                         depth.data_ptr(), seg.data_ptr() if seg is not None else None, self._stream(), source=1 if delayed else 0)
         return depth, seg
+
+    # ------------------------------------------------------------------ colour cameras (appearance.py: ColorCameras)
+    _scene_shading = _appearance.ALOHA_SHADING
+
+    def _scene_colors(self):
+        return _appearance.aloha_colors(self.meta)
+
+    def render_color(self, camera, height: int, width: int, env_ids=None, colors=None, shading=None, normals: bool = False, depth: bool = False,
+                     segmentation: bool = False, delayed: bool = False):
+        """Colour images of the collision geometry, by ray casting and shading on the GPU (so101_tree_render_color).
+
+        camera, env_ids, delayed: as in render_depth.  colors: None (the scene's table, appearance.aloha_colors), a float32 [ngeom, 3]
+        array or tensor, [n_envs, ngeom, 3] for colours per env (the rendered env's row is used), or a dict {anything geom_group()
+        takes: rgb} applied over the scene's table.  shading: an appearance.Shading, None = appearance.ALOHA_SHADING.
+        Returns appearance.ColorImages(rgb, normal, depth, seg) on the env's device: rgb uint8 [n, ncam, height, width, 3]; with
+        normals=True the world-frame unit surface normal float32 [n, ncam, height, width, 3] (0 where the ray hits nothing); with
+        depth / segmentation what render_depth returns, bit for bit; None otherwise.  This is not MuJoCo's renderer: what is drawn is
+        the collision geometry of render_depth, flat-coloured per geom and Lambert-shaded by directional lights - no textures, shadows,
+        specular term, visual-only meshes or positional lights."""
+        from . import cameras as _cameras
+        cams = [c.with_body_ids(self.meta["body_names"]) for c in _cameras.resolve(camera, _cameras.ALOHA_CAMERAS)]
+        if delayed and not self._with_state:
+            raise ValueError("render_color(delayed=True) needs the physics-state delay line: create the environment with physics_state=True")
+        return self._render_color(cams, height, width, env_ids, colors, shading, normals, depth, segmentation, source=1 if delayed else 0)
 
     # ------------------------------------------------------------------ Cartesian tool control (tools.py)
     def _resolve_tool(self, tool):

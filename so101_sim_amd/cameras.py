@@ -1,5 +1,7 @@
 """Cameras of the depth / segmentation renderer (`so101_render` / `so101_tree_render`, include/so101.h;
-`BatchedEnvironment.render_depth`, `AlohaEnvironment.render_depth`).
+`BatchedEnvironment.render_depth`, `AlohaEnvironment.render_depth`) and of the colour renderer on top of it (`so101_render_color` /
+`so101_tree_render_color`; `render_color` of both environments, appearance.py): the same collision geometry, flat-coloured per geom and
+Lambert-shaded by directional lights - not MuJoCo's renderer, no textures, shadows, specular term, visual-only meshes or positional lights.
 
 What is rendered is the COLLISION geometry the kernels step - depth along the optical axis and the geom index per
 pixel - not RGB: the reference's images come from MuJoCo's renderer with its visual meshes, materials and lights

@@ -784,6 +784,36 @@ int so101_render(so101_sim* s, const so101_camera* cams, int ncam, int height, i
   return SO101_OK;
 }
 
+// ---- colour cameras (csrc/so101_shade.hpp): so101_render's two kernels, then k_shade on what they left
+int so101_render_color(so101_sim* s, const so101_camera* cams, int ncam, int height, int width, const int32_t* env_index, int n_render,
+                       const so101_shading* shading, const float* geom_rgb, int rgb_per_env, const so101_color_out* out, void* stream) {
+  REQUIRE_BOUND(s);
+  RenderCams rc{};
+  ShadeParams sp{};
+  if (!render_arguments(s, "so101_render_color", cams, ncam, height, width, n_render, s->n_envs, env_index != nullptr, true, NDYN - 1, rc)) return SO101_ERR_ARG;
+  if (!shade_arguments(s, "so101_render_color", shading, geom_rgb, out, sp)) return SO101_ERR_ARG;
+  RenderHost& R = s->render;
+  if (R.has_meshes() && !R.planes_set) { s->err = "so101_render_color: the scene has mesh geoms and no hull planes (call so101_set_hull_planes)"; return SO101_ERR_STATE; }
+  GUARD_DEVICE(s);
+  const size_t cap = R.cap, px_bytes = R.pixel_bytes();
+  const bool shade = out->rgb || out->normal;
+  const bool grown = R.reserve(s, (size_t)n_render) && (!shade || (out->depth && out->seg) || R.reserve_pixels(s, (size_t)n_render * ncam * height * width));
+  s->scratch_bytes += R.frame_bytes() * R.cap - R.frame_bytes() * cap;          // (the scratch it had is gone when the growth failed)
+  s->scratch_bytes += R.pixel_bytes() - px_bytes;
+  if (!grown) return SO101_ERR_HIP;
+  float* depth = out->depth ? out->depth : (shade ? R.px_depth : nullptr);
+  int* seg = out->seg ? (int*)out->seg : (shade ? R.px_seg : nullptr);
+  so101::launch_render(n_render, (hipStream_t)stream, s->dm, make_params(s), s->buf, (const int*)env_index, rc, ncam, height, width,
+                       R.hull_planes, R.plane_adr, R.frames, R.cams, depth, seg);
+  LAUNCH_CHECK(s, "k_render");
+  if (shade) {
+    so101::launch_shade_image(n_render, (hipStream_t)stream, s->dm, R.frames, R.cams, R.hull_planes, R.plane_adr, ncam, height, width, depth, seg, geom_rgb, rgb_per_env != 0,
+                              (const int*)env_index, sp, out->rgb, out->normal);
+    LAUNCH_CHECK(s, "k_shade");
+  }
+  return SO101_OK;
+}
+
 // ---- Cartesian tool control (csrc/so101_tool_chain.hpp)
 namespace {
 // The chain of a tool on an arm link: the base as the root, one hinge column per arm link up to the tool's; the links beyond it are I/O columns

@@ -232,6 +232,8 @@ struct RenderHost {
   bool planes_set = false;
   float *frames = nullptr, *cams = nullptr;      // device [cap][ngeom][RENDER_FRAME], [cap][RENDER_MAXCAM][RENDER_CAMFRAME]
   size_t cap = 0;
+  float* px_depth = nullptr; int* px_seg = nullptr;      // device [px_cap] each: depth / seg of a colour render whose caller asked for neither
+  size_t px_cap = 0;
   int ngeom = 0;
   void load(const BlobView& b) { ngeom = b.I("ngeom")[0]; gtype = b.I("geom_type"); vertadr = b.I("geom_vertadr"); vertnum = b.I("geom_vertnum"); vert = b.F("mesh_vert"); }
   bool has_meshes() const { for (int t : gtype) if (t == G_MESH) return true; return false; }
@@ -262,6 +264,20 @@ struct RenderHost {
     if (!dev_alloc(s, &frames, n_render * ngeom * RENDER_FRAME, -1, "hipMalloc(render)") ||
         !dev_alloc(s, &cams, n_render * RENDER_MAXCAM * RENDER_CAMFRAME, -1, "hipMalloc(render)")) return false;
     cap = n_render;
+    return true;
+  }
+  // pixel scratch of the colour renders (so101_render_color / so101_tree_render_color): k_shade reads the depth and seg k_render wrote, so a
+  // caller who asks for neither gets them here.  Grown like the frames scratch; 8 bytes per pixel (SO101_INFO_SCRATCH_BYTES counts them)
+  size_t pixel_bytes() const { return (sizeof(float) + sizeof(int)) * px_cap; }
+  bool reserve_pixels(HostHandle* s, size_t npx) {
+    if (npx <= px_cap) return true;
+    for (void* p : {(void*)px_depth, (void*)px_seg}) {
+      auto it = std::find(s->owned.begin(), s->owned.end(), p);
+      if (p && it != s->owned.end()) { s->owned.erase(it); (void)hipFree(p); }
+    }
+    px_depth = nullptr; px_seg = nullptr; px_cap = 0;
+    if (!dev_alloc(s, &px_depth, npx, -1, "hipMalloc(render)") || !dev_alloc(s, &px_seg, npx, -1, "hipMalloc(render)")) return false;
+    px_cap = npx;
     return true;
   }
 };
@@ -311,6 +327,34 @@ inline bool render_arguments(HostHandle* s, const char* api, const so101_camera*
     rc.cam[k].body = cams[k].body;
     rc.cam[k].scale = (float)(2.0 * std::tan(0.5 * (double)cams[k].fovy_deg * 3.14159265358979323846 / 180.0) / (double)height);
     memcpy(rc.cam[k].pos, cams[k].pos, sizeof rc.cam[k].pos); memcpy(rc.cam[k].mat, cams[k].mat, sizeof rc.cam[k].mat);
+  }
+  return true;
+}
+
+// The arguments of a colour render beyond those of render_arguments(): the shading into the kernel argument.  false (SO101_ERR_ARG) with s->err set.
+inline bool shade_arguments(HostHandle* s, const char* api, const so101_shading* shading, const float* geom_rgb, const so101_color_out* out, ShadeParams& S) {
+  const std::string a(api);
+  if (!shading) { s->err = a + ": NULL shading"; return false; }
+  if (!geom_rgb) { s->err = a + ": NULL geom_rgb"; return false; }
+  if (!out) { s->err = a + ": NULL out"; return false; }
+  if (!out->rgb && !out->normal && !out->depth && !out->seg) { s->err = a + ": no output pointer at all"; return false; }
+  if (shading->nlight < 0 || shading->nlight > SO101_MAX_LIGHTS) { s->err = a + ": nlight must be 0 .. " + std::to_string(SO101_MAX_LIGHTS); return false; }
+  auto colour = [](const float* v) { for (int k = 0; k < 3; k++) if (!(std::isfinite(v[k]) && v[k] >= 0.f)) return false; return true; };
+  if (!colour(shading->ambient)) { s->err = a + ": ambient must be finite and >= 0"; return false; }
+  if (!colour(shading->background)) { s->err = a + ": background must be finite and >= 0"; return false; }
+  S = ShadeParams{};
+  memcpy(S.ambient, shading->ambient, sizeof S.ambient); memcpy(S.background, shading->background, sizeof S.background);
+  S.nlight = shading->nlight;
+  for (int l = 0; l < shading->nlight; l++) {
+    const auto& L = shading->light[l];
+    if (!colour(L.diffuse)) { s->err = a + ": light " + std::to_string(l) + ": diffuse must be finite and >= 0"; return false; }
+    if (!L.headlight) {
+      const double len = std::sqrt((double)L.dir[0] * L.dir[0] + (double)L.dir[1] * L.dir[1] + (double)L.dir[2] * L.dir[2]);
+      if (!(std::fabs(len - 1.0) <= 1e-4)) { s->err = a + ": light " + std::to_string(l) + ": dir is no unit vector (| |dir| - 1 | > 1e-4)"; return false; }
+      memcpy(S.dir[l], L.dir, sizeof S.dir[l]);
+    }
+    memcpy(S.diffuse[l], L.diffuse, sizeof S.diffuse[l]);
+    S.headlight[l] = L.headlight != 0;
   }
   return true;
 }

@@ -41,6 +41,11 @@ void launch_reward(int n_envs, hipStream_t st, const DevModel* m, const StepPara
 // general-tree engine after its k_tree_render_frames, tu_tree.hip).  launch_render: the SO100 frames kernel (so101_camera.hpp), then the image.
 void launch_render_image(int n_render, hipStream_t st, const DevModel* m, const float* frames, const float* camframes, const float* planes, const int* plane_adr,
                          int ncam, int height, int width, float* depth, int* seg);
+// colour cameras.  launch_shade_image: k_shade (so101_shade.hpp) on the grid of k_render, after it on the same stream, from the depth / seg it wrote -
+// like k_render ONE copy in the library, called by both engines.  rgb / normal: either may be NULL.
+void launch_shade_image(int n_render, hipStream_t st, const DevModel* m, const float* frames, const float* camframes, const float* planes, const int* plane_adr,
+                        int ncam, int height, int width, const float* depth, const int* seg, const float* geom_rgb, int rgb_per_env, const int* env_index,
+                        const ShadeParams& S, unsigned char* rgb, float* normal);
 void launch_render(int n_render, hipStream_t st, const DevModel* m, const StepParams& P, const DevBuffers& B, const int* env_index, const RenderCams& cams,
                    int ncam, int height, int width, const float* planes, const int* plane_adr, float* frames, float* camframes,
                    float* depth, int* seg);

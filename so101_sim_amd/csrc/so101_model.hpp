@@ -293,6 +293,9 @@ struct ChainParams { const DevModel* m; StepParams P; DevBuffers B; EventBuffers
 #define RENDER_CAMFRAME 13       // floats per camera: pos[3], mat[9] (world from camera; columns x right, y up, z; the camera looks along -z), pixel scale
 struct RenderCam { int body; float pos[3], mat[9], scale; };      // body: -1 world, else as geom_dyn numbers the bodies (SO100: 0 .. NDYN - 1, tree: the body id); scale = 2 tan(fovy / 2) / H
 struct RenderCams { RenderCam cam[RENDER_MAXCAM]; };
+// ---- colour cameras (so101_shade.hpp): the shading of one so101_render_color / so101_tree_render_color call (a kernel argument)
+#define SHADE_MAXLIGHT 4         // SO101_MAX_LIGHTS of include/so101.h
+struct ShadeParams { float ambient[3], background[3]; int nlight; float dir[SHADE_MAXLIGHT][3], diffuse[SHADE_MAXLIGHT][3]; int headlight[SHADE_MAXLIGHT]; };
 
 // ---- contact sensing: the outputs of one so101_contacts / so101_tree_contacts call (its geom-group pairs: TouchPairsT of so101_contact_report.hpp)
 #define TOUCH_MAX_PAIRS 16        // SO101_TOUCH_MAX_PAIRS of include/so101.h

@@ -1,9 +1,10 @@
-// Translation unit: physics-only stepping, the parity-test stage dump, contact sensing, proximity sensing, reward, episode bookkeeping (Newton), the cameras, Cartesian tool control
+// Translation unit: physics-only stepping, the parity-test stage dump, contact sensing, proximity sensing, reward, episode bookkeeping (Newton), the cameras (depth / segmentation and colour), Cartesian tool control
 // of both engines (the chain kernels for 6 columns - SO100 - and 8 - the general-tree engine, both builds).
 #include "so101_kernels.hpp"
 #include "so101_contacts.hpp"
 #include "so101_proximity.hpp"
 #include "so101_camera.hpp"
+#include "so101_shade.hpp"
 #include "so101_tool_chain.hpp"
 #include "so101_launch.hpp"
 
@@ -61,6 +62,13 @@ void launch_render_image(int n_render, hipStream_t st, const DevModel* m, const 
   unsigned int tiles = (unsigned int)((height + 7) / 8) * (unsigned int)((width + 7) / 8);
   hipLaunchKernelGGL(k_render, dim3((unsigned int)n_render * (unsigned int)ncam * tiles), dim3(64), 0, st, m, frames, camframes, planes, plane_adr, ncam, height, width,
                      depth, seg);
+}
+void launch_shade_image(int n_render, hipStream_t st, const DevModel* m, const float* frames, const float* camframes, const float* planes, const int* plane_adr,
+                        int ncam, int height, int width, const float* depth, const int* seg, const float* geom_rgb, int rgb_per_env, const int* env_index,
+                        const ShadeParams& S, unsigned char* rgb, float* normal) {
+  unsigned int tiles = (unsigned int)((height + 7) / 8) * (unsigned int)((width + 7) / 8);
+  hipLaunchKernelGGL(k_shade, dim3((unsigned int)n_render * (unsigned int)ncam * tiles), dim3(64), 0, st, m, frames, camframes, planes, plane_adr, ncam, height, width,
+                     depth, seg, geom_rgb, rgb_per_env, env_index, S, rgb, normal);
 }
 void launch_render(int n_render, hipStream_t st, const DevModel* m, const StepParams& P, const DevBuffers& B, const int* env_index, const RenderCams& cams,
                    int ncam, int height, int width, const float* planes, const int* plane_adr, float* frames, float* camframes,

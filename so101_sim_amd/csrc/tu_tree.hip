@@ -289,6 +289,37 @@ int TAPI(render)(TreeHandle* s, const so101_camera* cams, int ncam, int height, 
   return hip_ok(s, hipGetLastError(), "k_render") ? SO101_OK : SO101_ERR_HIP;
 }
 
+// ---- colour cameras (so101_shade.hpp): the two kernels of render above, then the library's one k_shade through so101::launch_shade_image
+int TAPI(render_color)(TreeHandle* s, const so101_camera* cams, int ncam, int height, int width, const int32_t* env_index, int n_render, int source,
+                       const so101_shading* shading, const float* geom_rgb, int rgb_per_env, const so101_color_out* out, void* stream) {
+  if (!s) return SO101_ERR_ARG;
+  RenderCams rc{};
+  ShadeParams sp{};
+  if (!render_arguments(s, "so101_tree_render_color", cams, ncam, height, width, n_render, s->n_envs, env_index != nullptr, true, s->hm.nbody - 1, rc)) return SO101_ERR_ARG;
+  if (source != 0 && source != 1) { s->err = "so101_tree_render_color: source must be 0 (the bound qpos) or 1 (the delayed physics-state line)"; return SO101_ERR_ARG; }
+  if (!shade_arguments(s, "so101_tree_render_color", shading, geom_rgb, out, sp)) return SO101_ERR_ARG;
+  RenderHost& R = s->render;
+  if (R.has_meshes() && !R.planes_set) { s->err = "so101_tree_render_color: the scene has mesh geoms and no hull planes (call so101_tree_set_hull_planes)"; return SO101_ERR_STATE; }
+  if (source == 0 && !s->bound) { s->err = "so101_tree_render_color before so101_tree_bind_state"; return SO101_ERR_STATE; }
+  if (source == 1 && !s->env.ps_delayed) { s->err = "so101_tree_render_color: source 1 needs the physics-state line (so101_tree_bind_physics_state)"; return SO101_ERR_STATE; }
+  GUARD_DEVICE(s);
+  const bool shade = out->rgb || out->normal;
+  if (!R.reserve(s, (size_t)n_render)) return SO101_ERR_HIP;
+  if (shade && !(out->depth && out->seg) && !R.reserve_pixels(s, (size_t)n_render * ncam * height * width)) return SO101_ERR_HIP;
+  float* depth = out->depth ? out->depth : (shade ? R.px_depth : nullptr);
+  int* seg = out->seg ? (int*)out->seg : (shade ? R.px_seg : nullptr);
+  const float* q = source == 0 ? s->buf.qpos : s->env.ps_delayed;
+  const size_t lane_stride = source == 0 ? (size_t)s->n_envs : 1, env_stride = source == 0 ? 1 : (size_t)(s->hm.nq + s->hm.nv);
+  hipLaunchKernelGGL(k_tree_render_frames, dim3(n_render), dim3(64), 0, (hipStream_t)stream, s->dm, s->dg, q, lane_stride, env_stride, s->n_envs, (const int*)env_index, rc, ncam,
+                     R.frames, R.cams);
+  so101::launch_render_image(n_render, (hipStream_t)stream, s->dg, R.frames, R.cams, R.hull_planes, R.plane_adr, ncam, height, width, depth, seg);
+  if (!hip_ok(s, hipGetLastError(), "k_render")) return SO101_ERR_HIP;
+  if (shade)
+    so101::launch_shade_image(n_render, (hipStream_t)stream, s->dg, R.frames, R.cams, R.hull_planes, R.plane_adr, ncam, height, width, depth, seg, geom_rgb, rgb_per_env != 0,
+                              (const int*)env_index, sp, out->rgb, out->normal);
+  return hip_ok(s, hipGetLastError(), "k_shade") ? SO101_OK : SO101_ERR_HIP;
+}
+
 // ---- Cartesian tool control (so101_tool_chain.hpp)
 int TAPI(tool_chain)(TreeHandle* s, int body, int32_t* dof, int32_t* qposadr, int32_t* jnt_type) {
   if (!s) return SO101_ERR_ARG;

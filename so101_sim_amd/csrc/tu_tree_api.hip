@@ -30,6 +30,7 @@
   int so101_tree##V##_step(void*, const float*, float*, float*, float*, uint8_t*, void*);                                                     \
   int so101_tree##V##_set_hull_planes(void*, const float*, const int32_t*);                                                                   \
   int so101_tree##V##_render(void*, const so101_camera*, int, int, int, const int32_t*, int, int, float*, int32_t*, void*);                    \
+  int so101_tree##V##_render_color(void*, const so101_camera*, int, int, int, const int32_t*, int, int, const so101_shading*, const float*, int, const so101_color_out*, void*); \
   int so101_tree##V##_tool_chain(void*, int, int32_t*, int32_t*, int32_t*);                                                                    \
   int so101_tree##V##_ik_default_config(void*, int, so101_tree_ik_config*);                                                                    \
   int so101_tree##V##_tool_pose(void*, const so101_tree_tool*, const float*, const int32_t*, int, float*, float*, float*, void*);              \
@@ -111,6 +112,10 @@ int so101_tree_set_hull_planes(so101_tree* s, const float* planes, const int32_t
 int so101_tree_render(so101_tree* s, const so101_camera* cams, int ncam, int height, int width, const int32_t* env_index, int n_render, int source,
                       float* depth, int32_t* seg, void* stream) {
   return s ? FWD(render, cams, ncam, height, width, env_index, n_render, source, depth, seg, stream) : SO101_ERR_ARG;
+}
+int so101_tree_render_color(so101_tree* s, const so101_camera* cams, int ncam, int height, int width, const int32_t* env_index, int n_render, int source,
+                            const so101_shading* shading, const float* geom_rgb, int rgb_per_env, const so101_color_out* out, void* stream) {
+  return s ? FWD(render_color, cams, ncam, height, width, env_index, n_render, source, shading, geom_rgb, rgb_per_env, out, stream) : SO101_ERR_ARG;
 }
 int so101_tree_tool_chain(const so101_tree* s, int body, int32_t* dof, int32_t* qposadr, int32_t* jnt_type) { return s ? FWD(tool_chain, body, dof, qposadr, jnt_type) : SO101_ERR_ARG; }
 int so101_tree_ik_default_config(const so101_tree* s, int body, so101_tree_ik_config* cfg) { return s ? FWD(ik_default_config, body, cfg) : SO101_ERR_ARG; }

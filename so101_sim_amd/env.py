@@ -24,6 +24,7 @@ from . import native
 from ._dmenv import BoundedArray, Array, StepType, TimeStep
 from .calibration import SO101Calibration
 from .model import scenes
+from . import appearance as _appearance
 from . import contacts as _contacts
 from . import proximity as _proximity
 from .tool_control import ToolControl
@@ -119,7 +120,7 @@ class _PhysicsView:
         raise NotImplementedError("rendering is outside the MI355X hot path (SURVEY.md 8b)")
 
 
-class BatchedEnvironment(ToolControl, _contacts.ContactSensing, _proximity.ProximitySensing):
+class BatchedEnvironment(ToolControl, _contacts.ContactSensing, _proximity.ProximitySensing, _appearance.ColorCameras):
     def __init__(self, task: SO100HandOverTask, n_envs: int = 1, time_limit: float = float("inf"),
                  random_state=None, device=None, env_id_base: int = 0, solver_iterations: int = 0,
                  solver_tolerance: float = -1.0, settle_max_substeps: int = 1000, solver: str = "newton",
@@ -388,6 +389,27 @@ class BatchedEnvironment(ToolControl, _contacts.ContactSensing, _proximity.Proxi
         self.sim.render([c.spec() for c in cams], height, width, idx.data_ptr() if idx is not None else None, n,
                         depth.data_ptr(), seg.data_ptr() if seg is not None else None, self._stream())
         return depth, seg
+
+    # ------------------------------------------------------------------ colour cameras (appearance.py: ColorCameras)
+    _scene_shading = _appearance.SO100_SHADING
+
+    def _scene_colors(self):
+        return _appearance.so100_colors(self.meta)
+
+    def render_color(self, camera, height: int, width: int, env_ids=None, colors=None, shading=None, normals: bool = False, depth: bool = False,
+                     segmentation: bool = False):
+        """Colour images of the collision geometry at the current state, by ray casting and shading on the GPU (so101_render_color).
+
+        camera, env_ids: as in render_depth.  colors: None (the scene's table, appearance.so100_colors), a float32 [ngeom, 3] array or
+        tensor, [n_envs, ngeom, 3] for colours per env (the rendered env's row is used), or a dict {anything geom_group() takes: rgb}
+        applied over the scene's table.  shading: an appearance.Shading, None = appearance.SO100_SHADING.
+        Returns appearance.ColorImages(rgb, normal, depth, seg) on the env's device: rgb uint8 [n, ncam, height, width, 3]; with
+        normals=True the world-frame unit surface normal float32 [n, ncam, height, width, 3] (0 where the ray hits nothing); with
+        depth / segmentation what render_depth returns, bit for bit; None otherwise.  This is not MuJoCo's renderer: what is drawn is
+        the collision geometry of render_depth, flat-coloured per geom and Lambert-shaded by directional lights - no textures, shadows,
+        specular term, visual-only meshes or positional lights."""
+        from . import cameras as _cameras
+        return self._render_color(_cameras.resolve(camera), height, width, env_ids, colors, shading, normals, depth, segmentation)
 
     # ------------------------------------------------------------------ Cartesian tool control (tools.py)
     def _resolve_tool(self, tool):

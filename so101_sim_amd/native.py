@@ -32,10 +32,10 @@ EXPORTS = (
     "so101_version", "so101_max_contacts", "so101_create", "so101_destroy", "so101_default_config",
     "so101_configure", "so101_bind_state", "so101_bind_physics_state", "so101_set_reset_pool", "so101_compute_settled", "so101_set_settled_store", "so101_reset", "so101_settle", "so101_begin_episode", "so101_step", "so101_physics", "so101_reward",
     "so101_get_returns", "so101_get_diag", "so101_get_events", "so101_debug_forward", "so101_debug_candidates", "so101_debug_stages", "so101_get_info", "so101_debug_chain_stats", "so101_last_error",
-    "so101_set_hull_planes", "so101_render", "so101_ik_default_config", "so101_tool_pose", "so101_tool_ik", "so101_contacts", "so101_proximity",
+    "so101_set_hull_planes", "so101_render", "so101_render_color", "so101_ik_default_config", "so101_tool_pose", "so101_tool_ik", "so101_contacts", "so101_proximity",
     "so101_tree_create", "so101_tree_destroy", "so101_tree_dims", "so101_tree_last_plan", "so101_tree_bind_state", "so101_tree_configure", "so101_tree_physics",
     "so101_tree_debug_forward", "so101_tree_get_diag", "so101_tree_last_error", "so101_tree_obs_dim", "so101_tree_bind_env",
-    "so101_tree_configure_env", "so101_tree_bind_physics_state", "so101_tree_reset", "so101_tree_step", "so101_tree_set_hull_planes", "so101_tree_render", "so101_tree_begin_episode", "so101_tree_settle", "so101_tree_compute_settled", "so101_tree_set_settled_store",
+    "so101_tree_configure_env", "so101_tree_bind_physics_state", "so101_tree_reset", "so101_tree_step", "so101_tree_set_hull_planes", "so101_tree_render", "so101_tree_render_color", "so101_tree_begin_episode", "so101_tree_settle", "so101_tree_compute_settled", "so101_tree_set_settled_store",
     "so101_tree_tool_chain", "so101_tree_ik_default_config", "so101_tree_tool_pose", "so101_tree_tool_ik", "so101_tree_contacts", "so101_tree_proximity",
 )
 
@@ -68,6 +68,42 @@ def camera_array(cams):
         arr[k].mat[:] = [float(x) for x in mat]
         arr[k].fovy_deg = float(fovy)
     return arr
+
+
+MAX_LIGHTS = 4          # SO101_MAX_LIGHTS
+
+
+class LightSpec(C.Structure):
+    _fields_ = [("dir", C.c_float * 3), ("diffuse", C.c_float * 3), ("headlight", C.c_int32)]
+
+
+class ShadingSpec(C.Structure):
+    """so101_shading of include/so101.h"""
+    _fields_ = [("ambient", C.c_float * 3), ("background", C.c_float * 3), ("nlight", C.c_int32), ("light", LightSpec * MAX_LIGHTS)]
+
+
+class ColorOut(C.Structure):
+    """so101_color_out of include/so101.h: device addresses, any may be None, not all"""
+    _fields_ = [("rgb", C.c_void_p), ("normal", C.c_void_p), ("depth", C.c_void_p), ("seg", C.c_void_p)]
+
+
+def shading_struct(shading) -> ShadingSpec:
+    """(ambient[3], background[3], lights) -> so101_shading; a light is (dir[3] or None for a headlight, diffuse[3]).  A ShadingSpec passes through."""
+    if isinstance(shading, ShadingSpec):
+        return shading
+    ambient, background, lights = shading
+    lights = list(lights)
+    if len(lights) > MAX_LIGHTS:
+        raise ValueError(f"at most {MAX_LIGHTS} lights, got {len(lights)}")
+    out = ShadingSpec()
+    out.ambient[:] = [float(x) for x in ambient]
+    out.background[:] = [float(x) for x in background]
+    out.nlight = len(lights)
+    for k, (direction, diffuse) in enumerate(lights):
+        out.light[k].headlight = int(direction is None)
+        out.light[k].dir[:] = [0.0, 0.0, 0.0] if direction is None else [float(x) for x in direction]
+        out.light[k].diffuse[:] = [float(x) for x in diffuse]
+    return out
 
 
 class ToolSpec(C.Structure):
@@ -188,6 +224,7 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.so101_last_error.argtypes = [vp]
     L.so101_set_hull_planes.argtypes = [vp, vp, vp]
     L.so101_render.argtypes = [vp, C.POINTER(CameraSpec), C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp]
+    L.so101_render_color.argtypes = [vp, C.POINTER(CameraSpec), C.c_int, C.c_int, C.c_int, vp, C.c_int, C.POINTER(ShadingSpec), vp, C.c_int, C.POINTER(ColorOut), vp]
     L.so101_ik_default_config.argtypes = [vp, C.POINTER(IkConfig)]
     L.so101_tool_pose.argtypes = [vp, C.POINTER(ToolSpec), vp, vp, C.c_int, vp, vp, vp, vp]
     L.so101_tool_ik.argtypes = [vp, C.POINTER(ToolSpec), C.POINTER(IkConfig), vp, vp, vp, vp, C.c_int, vp, vp, vp, vp]
@@ -323,6 +360,15 @@ class Sim:
         arr = camera_array(cams)
         self._check(self.L.so101_render(self.h, arr, len(cams), int(height), int(width), env_index, int(n_render), depth, seg, stream), "so101_render")
 
+    def render_color(self, cams, height: int, width: int, env_index, n_render: int, shading, geom_rgb, rgb_per_env: bool = False,
+                     rgb=None, normal=None, depth=None, seg=None, stream=0):
+        """so101_render_color.  cams as for render; shading: what shading_struct() takes; geom_rgb / env_index / rgb / normal / depth / seg: raw
+        device addresses or None (geom_rgb [ngeom, 3] float32, or [n_envs, ngeom, 3] with rgb_per_env)"""
+        arr = camera_array(cams)
+        out = ColorOut(rgb, normal, depth, seg)
+        self._check(self.L.so101_render_color(self.h, arr, len(cams), int(height), int(width), env_index, int(n_render), C.byref(shading_struct(shading)), geom_rgb,
+                                              int(bool(rgb_per_env)), C.byref(out), stream), "so101_render_color")
+
     def ik_config(self, **kw) -> IkConfig:
         """so101_ik_default_config (mode 1, 60 iterations, 1e-4 m, 1e-3 rad, the model's joint ranges) with the given fields replaced;
         q_lo / q_hi take sequences of 6"""
@@ -397,6 +443,8 @@ class TreeSim:
         L.so101_tree_set_settled_store.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4
         L.so101_tree_set_hull_planes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.so101_tree_render.argtypes = [C.c_void_p, C.POINTER(CameraSpec), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.so101_tree_render_color.argtypes = [C.c_void_p, C.POINTER(CameraSpec), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(ShadingSpec), C.c_void_p, C.c_int,
+                                              C.POINTER(ColorOut), C.c_void_p]
         vp = C.c_void_p
         L.so101_tree_tool_chain.argtypes = [vp, C.c_int, vp, vp, vp]
         L.so101_tree_ik_default_config.argtypes = [vp, C.c_int, C.POINTER(TreeIkConfig)]
@@ -504,6 +552,14 @@ class TreeSim:
         device addresses or None; source 0: the bound qpos, 1: the delayed physics-state line (so101_tree_bind_physics_state)"""
         arr = camera_array(cams)
         self._check(self.L.so101_tree_render(self.h, arr, len(cams), int(height), int(width), env_index, int(n_render), int(source), depth, seg, stream), "so101_tree_render")
+
+    def render_color(self, cams, height: int, width: int, env_index, n_render: int, shading, geom_rgb, rgb_per_env: bool = False,
+                     rgb=None, normal=None, depth=None, seg=None, stream=0, source: int = 0):
+        """so101_tree_render_color: native.Sim.render_color on this engine; cams and source as for render"""
+        arr = camera_array(cams)
+        out = ColorOut(rgb, normal, depth, seg)
+        self._check(self.L.so101_tree_render_color(self.h, arr, len(cams), int(height), int(width), env_index, int(n_render), int(source), C.byref(shading_struct(shading)),
+                                                   geom_rgb, int(bool(rgb_per_env)), C.byref(out), stream), "so101_tree_render_color")
 
     def tool_chain(self, body: int):
         """The columns of a tool on body `body` (so101_tree_tool_chain): (dof indices, qpos addresses, joint types 1 hinge / 3 slide), root first"""
