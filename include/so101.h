@@ -469,7 +469,8 @@ void so101_tree_destroy(so101_tree* sim);
  * otherwise the 64-dof / 256-geom / 160-contact one of the Dining scenes) */
 int so101_tree_dims(const so101_tree* sim, int* dims);
 /* What the last so101_tree_step of this handle enqueued, as the library counted it (not a host-side copy of the rule): out[4] = env slices,
- * kernel launches, memsets, path (0: no step yet, 1: the single kernel k_tree_step, 2: the launch chain).  bench.py reports it as evidence. */
+ * kernel launches, memsets, path (0: no step yet, 1: the single kernel k_tree_step, 2: the launch chain).  A step that returns SO101_ERR_HIP
+ * leaves the counts of the last step that was enqueued whole.  bench.py reports it as evidence. */
 int so101_tree_last_plan(const so101_tree* sim, int* out);
 int so101_tree_bind_state(so101_tree* sim, float* qpos, float* qvel, float* ctrl, float* warmstart);
 /* solver_iterations <= 0 / solver_tolerance < 0 keep the model's (100, 1e-8) */

@@ -60,7 +60,7 @@ struct so101_sim : HostHandle {      // (so101_host.hpp: device, owned allocatio
   ChainParams chain_host{};                // what it holds
   bool chain_params_valid = false;
   PipeBuffers pipe{};          // scratch of the pipelined step (group 0's view; the groups differ in work/counters)
-  static constexpr int MAXGROUPS = 8;
+  static constexpr int MAXGROUPS = STEP_PLAN_MAX_SLICES;
   StreamLanes<MAXGROUPS> groups;           // one stream per launch chain (so101_host.hpp)
   EventBuffers ev{};           // per-env flag accumulator + global event counters (so101_get_events)
   // captured launch sequence of the pipelined step (see so101_step)
@@ -466,49 +466,22 @@ int so101_begin_episode(so101_sim* s, void* stream) {
 static int enqueue_pipelined(so101_sim* s, hipStream_t st, const so101::StepIO& io) {
   StepParams P = make_params(s);
   PrepBuffers C = prep_view(s);
-  // groups = 0 (default): four chains when the HIP runtime was given enough hardware queues for them, else three.
-  // The runtime maps streams onto GPU_MAX_HW_QUEUES (default 4) hardware queues; this step uses chains + 2 streams,
-  // and streams that share a queue serialise: with the default, 4 chains run at 400 k env-steps/s against 650 k for
-  // 3; with GPU_MAX_HW_QUEUES=8 (so101_sim_amd sets it when imported before HIP initialises) 4 chains reach 672 k.
-  // SO101_HW_QUEUES_EFFECTIVE: set by a host that knows the variable came too late for the runtime (so101_sim_amd/__init__.py)
-  static const int hwq = getenv("SO101_HW_QUEUES_EFFECTIVE") ? atoi(getenv("SO101_HW_QUEUES_EFFECTIVE"))
-                         : (getenv("GPU_MAX_HW_QUEUES") ? atoi(getenv("GPU_MAX_HW_QUEUES")) : 4);
-  int G = s->cfg.groups > 0 ? s->cfg.groups : (hwq >= 6 ? 4 : 3);
+  // what to launch is decided by the plan (so101_step_plan.hpp); this function executes it
+  const int n = s->n_envs, hwq = hw_queues();
+  const StepPlan plan = plan_so100_step(n, s->cfg.groups, hwq, read_step_knobs());
   static bool warned = false;
-  if (!warned && hwq < 6 && s->cfg.groups == 0 && s->n_envs >= 64) {
+  if (!warned && hwq < STEP_PLAN_QUEUES_FOR_FOUR_CHAINS && s->cfg.groups == 0 && n >= 64) {
     warned = true;
     fprintf(stderr, "libso101_hip: %d hardware queues (GPU_MAX_HW_QUEUES): the pipelined step runs three launch chains instead of four "
                     "(about 3 %% slower at 4096 envs); export GPU_MAX_HW_QUEUES=8 before HIP initialises\n", hwq);
   }
-  if (G > so101_sim::MAXGROUPS) G = so101_sim::MAXGROUPS;
-  int n = s->n_envs;
-  if (n < 64) G = 1;
-  s->last_chains = G;
-  // Slices of the cost-sorted env order (most expensive first), one launch chain each: 2 chains split at n/2, 3 at n/4
-  // and 5n/8, 4 and more in equal parts (re-measured in round 2 at 4096 envs: 1 chain 515 k, 2 618 k, 3 653 k, 4 672 k
-  // with enough hardware queues, 5-6 650 k env-steps/s; unequal 4-way splits are 1-2 % slower)
-  int bounds[so101_sim::MAXGROUPS + 1];
-  bounds[0] = 0;
-  if (G == 2) bounds[1] = n / 2;
-  if (G == 3) { bounds[1] = n / 4; bounds[2] = (5 * n) / 8; }
-  if (G > 3) for (int g = 1; g < G; g++) bounds[g] = (int)((long long)n * g / G);
-  bounds[G] = n;
-#ifdef SO101_DEBUG_CLOCKS
-  static const char* dbg_bounds = getenv("SO101_DEBUG_BOUNDS");     // profiling builds: "128,1024" = slice ends
-  if (dbg_bounds) {
-    G = 0; bounds[0] = 0;
-    for (const char* p = dbg_bounds; *p && G < so101_sim::MAXGROUPS - 1;) { int v = atoi(p); if (v > bounds[G] && v < n) bounds[++G] = v; while (*p && *p != ',') p++; if (*p) p++; }
-    bounds[++G] = n;
-  }
-#endif
-  // (equal slices - four chains - get the sorted envs dealt out, tu_pipe_solve.hip k_order; the three unequal slices keep the plain sorted order)
-  bool equal_slices = G > 1;
-  for (int g = 0; g < G && equal_slices; g++) equal_slices = bounds[g + 1] - bounds[g] == n / G;
-  so101::launch_order(st, s->pipe.cost, s->pipe.order, s->chain_cls, n, equal_slices && n % G == 0 ? G : 1);
+  const int G = plan.G;
+  s->last_chains = G; s->last_list_rows = plan.list_rows ? 1 : 0;
+  so101::launch_order(st, s->pipe.cost, s->pipe.order, s->chain_cls, n, plan.deal);
   LAUNCH_CHECK(s, "k_order");
   if (!s->groups.fork(s, st, G)) return SO101_ERR_HIP;
   for (int g = 0; g < G; g++) {
-    int e0 = bounds[g], ng = bounds[g + 1] - bounds[g];
+    const int e0 = plan.bounds[g], ng = plan.bounds[g + 1] - e0, nw = plan.waves[g];
     if (ng <= 0) continue;
     PipeBuffers W = s->pipe;
     W.counters = s->pipe.counters + 4 * MAXSUB * g;      // [MAXSUB][2] work items / cursor, then [MAXSUB][2] heavy / light items (so101_pipeline.hpp)
@@ -518,45 +491,7 @@ static int enqueue_pipelined(so101_sim* s, hipStream_t st, const so101::StepIO& 
     W.conres = s->pipe.conres + ((size_t)e0 * CONRES_PER_ENV + (size_t)g * MAXCAND) * CONRES_DIM;
     W.conres_cap = (unsigned int)ng * CONRES_PER_ENV + MAXCAND;
     W.items = s->pipe.items + ((size_t)e0 * CONRES_PER_ENV + (size_t)g * MAXCAND) * ITEM_WORDS;      // one work item per record position of the slice
-    static const int chunk_env = getenv("SO101_NARROW_CHUNK") ? atoi(getenv("SO101_NARROW_CHUNK")) : 0;          // (kernel experiments)
-    static const int chunk_env_l = getenv("SO101_NARROW_CHUNK_LIGHT") ? atoi(getenv("SO101_NARROW_CHUNK_LIGHT")) : 0;
-    // measured at 4096 envs (heavy / light pairs per fetch -> env-steps/s): 3/3 707 k, 1/3 684 k, 2/3 712 k, 2/4 720 k, 1/4 692 k, 2/2 679 k
-    // (a handful of envs: one pair per fetch - 16 wavefronts share an env's dozen pairs, and the step is a chain of dependent launches)
-    // (round 6, with the support-bound tables and the fast path for flat faces the light pairs no longer hide a second heavy pair behind the first:
-    //  heavy pairs one per fetch and 1.25 wavefronts per env 763 -> 781 k env-steps/s at 4096 envs, 439 -> 461 k at 2048, each alone +1 %; at 8192
-    //  envs 893 -> 880 k, so two per fetch and 1.5 wavefronts per env stay there)
-    // (round 5, work items + LDS hull pool of 1024 slots: light pairs per fetch 4 / 3 / 2 / 1 -> 718 / 736 / 740 / 604 k env-steps/s at 4096 envs - four
-    //  light pairs with a 512-slot hull among them overflow the pool and stage late -; 32 768 envs, row-pass instance: 4 -> 1078 k, 2 -> 938 k)
-    // bit 8: the row pass (four light pairs per wavefront, one per DPP row; so101 tu_narrow.hip).  Measured, round 5: 32 768 envs 996 k -> 1 067 k
-    // env-steps/s (first window 1.21 -> 1.35 M); 4096 envs 715 k -> 710 k (there the step follows the critical path of its slowest slice -
-    // heavy pairs, long Newton solves -, not the light pairs' instruction count), so it is on above 8192 envs
-    const char* rows_var = getenv("SO101_NARROW_ROWS");            // (tests and kernel experiments: read when the step is enqueued / captured, so a handle created after a change sees it)
-    const int rows_env = rows_var ? atoi(rows_var) : -1;
-    const bool rows = rows_env >= 0 ? rows_env != 0 : n > 8192;
-    // bit 9: the LIST row pass of the other instance (k_narrow<false>: four list-backed light pairs per wavefront, tu_narrow.hip), read like
-    // SO101_NARROW_ROWS.  A fetch from the light region then takes NARROW_CHUNK pairs: fast items stage no hull, so four of them cannot overflow the pool
-    // (the reason for two per fetch otherwise).
-    const char* lrows_var = getenv("SO101_NARROW_LIST_ROWS");
-    const int lrows_env = lrows_var ? atoi(lrows_var) : -1;
-    // Measured, round 7, env-steps/s, parent library against this one in alternating runs on one machine, three launch chains (profiles/README.md):
-    // 4096 envs 729.0 k -> 749.3 k with the pass and four light pairs per fetch (pass off: 733.4 k); 8192 envs 928.6 k -> 1078.7 k; 2048 envs
-    // 490.9 k -> 455.1 k, so the pass is on above 2048 envs only.  Knobs at 4096 envs with the pass on: light pairs per fetch 4 / 3 / 2 -> 743.9 /
-    // 752.3 / 728.6 k (heavy 1); heavy pairs per fetch 1 / 2 -> 743.9 / 769.8 k (light 4) - with the light chunks four times as fast the launch
-    // again ends on its heavy pairs, and two per fetch halve their atomics -; wavefronts per env 1.0 / 1.25 / 1.5 -> 745.4 / 743.9 / 747.2 k (no difference).
-    const bool list_rows = !rows && (lrows_env >= 0 ? lrows_env != 0 : (SO101_LIST_ROWS_DEFAULT && n > 2048));
-    s->last_list_rows = list_rows ? 1 : 0;
-    int ch = chunk_env >= 1 && chunk_env <= NARROW_CHUNK ? chunk_env : (n <= 4096 ? (list_rows && n > 2048 ? 2 : 1) : (n <= 8192 ? 2 : NARROW_CHUNK));
-    int cl = chunk_env_l >= 1 && chunk_env_l <= NARROW_CHUNK ? chunk_env_l : (list_rows ? NARROW_CHUNK : (n <= 16 ? 1 : (n <= 8192 ? 2 : NARROW_CHUNK)));
-    W.narrow_chunk = (unsigned int)ch | ((unsigned int)cl << 4) | (rows ? 256u : 0u) | (list_rows ? 512u : 0u);        // heavy region | light region | row pass | list row pass
-    // persistent narrowphase waves (they pull work items until the list is empty): 1.5 - 2 per env of the slice, at
-    // most what fills 256 CUs - a smaller narrowphase grid leaves slots to the other chains' solve kernels
-    // (round 4, with the heavy-first work list: 1.5 waves per env 725 k, 2 per env 718 k, 2.5 per env 697 k env-steps/s at 4096 envs)
-    static const int nw_env = getenv("SO101_NARROW_WAVES_Q") ? atoi(getenv("SO101_NARROW_WAVES_Q")) : 0;      // (kernel experiments: quarter waves per env)
-    const int nw_quarters = nw_env > 0 ? nw_env : (n <= 4096 ? 5 : (n <= 8192 ? 6 : 8));
-    int nw = (int)((long long)ng * nw_quarters / 4);
-    // (a handful of envs - the reference's own N = 1: a step is a chain of dependent single-env launches, so the pairs of an env are spread
-    //  over 16 wavefronts instead of queued on one or two)
-    nw = nw < 16 ? 16 : (nw < 4096 ? nw : 4096);
+    W.narrow_chunk = plan.narrow_chunk;
     hipStream_t gs;
     if (!s->groups.stream_of(s, g, &gs)) return SO101_ERR_HIP;
     if (!hip_ok(s, hipMemsetAsync(W.counters, 0, sizeof(int) * 4 * MAXSUB, gs), "hipMemsetAsync(pipe)")) return SO101_ERR_HIP;
@@ -721,8 +656,7 @@ long long so101_get_info(so101_sim* s, int what, void* stream) {
     case SO101_INFO_GRAPH_ACTIVE: return s->last_graph ? 1 : 0;
     case SO101_INFO_STEP_PATH: return s->last_path;
     case SO101_INFO_CHAINS: return s->last_chains;
-    case SO101_INFO_HW_QUEUES: return getenv("SO101_HW_QUEUES_EFFECTIVE") ? atoi(getenv("SO101_HW_QUEUES_EFFECTIVE"))
-                                      : (getenv("GPU_MAX_HW_QUEUES") ? atoi(getenv("GPU_MAX_HW_QUEUES")) : 4);
+    case SO101_INFO_HW_QUEUES: return hw_queues();
     case SO101_INFO_SCRATCH_BYTES: return (long long)s->scratch_bytes;
     case SO101_INFO_NARROW_LIST_ROWS: return s->last_list_rows;
     case SO101_INFO_SCHED_ABORTS: {
@@ -766,43 +700,28 @@ int so101_set_hull_planes(so101_sim* s, const float* planes, const int32_t* plan
   return SO101_OK;
 }
 
-int so101_render(so101_sim* s, const so101_camera* cams, int ncam, int height, int width, const int32_t* env_index, int n_render,
-                 float* depth, int32_t* seg, void* stream) {
-  REQUIRE_BOUND(s);
-  RenderCams rc{};
-  if (!render_arguments(s, "so101_render", cams, ncam, height, width, n_render, s->n_envs, env_index != nullptr, depth || seg, NDYN - 1, rc)) return SO101_ERR_ARG;
-  RenderHost& R = s->render;
-  if (R.has_meshes() && !R.planes_set) { s->err = "so101_render: the scene has mesh geoms and no hull planes (call so101_set_hull_planes)"; return SO101_ERR_STATE; }
-  GUARD_DEVICE(s);
-  const size_t cap = R.cap;
-  const bool grown = R.reserve(s, (size_t)n_render);
-  s->scratch_bytes += R.frame_bytes() * R.cap - R.frame_bytes() * cap;          // (the scratch it had is gone when the growth failed)
-  if (!grown) return SO101_ERR_HIP;
-  so101::launch_render(n_render, (hipStream_t)stream, s->dm, make_params(s), s->buf, (const int*)env_index, rc, ncam, height, width,
-                       R.hull_planes, R.plane_adr, R.frames, R.cams, depth, (int*)seg);
-  LAUNCH_CHECK(s, "k_render");
-  return SO101_OK;
-}
-
-// ---- colour cameras (csrc/so101_shade.hpp): so101_render's two kernels, then k_shade on what they left
-int so101_render_color(so101_sim* s, const so101_camera* cams, int ncam, int height, int width, const int32_t* env_index, int n_render,
-                       const so101_shading* shading, const float* geom_rgb, int rgb_per_env, const so101_color_out* out, void* stream) {
+// One body for so101_render and so101_render_color (csrc/so101_shade.hpp): the depth / seg call is the colour call without shading.  k_render's two
+// kernels, then - shading asked for - k_shade on what they left.  color: the colour call (outputs in `out`, else depth and seg)
+static int render_call(so101_sim* s, const char* api, bool color, const so101_camera* cams, int ncam, int height, int width, const int32_t* env_index, int n_render,
+                       const so101_shading* shading, const float* geom_rgb, int rgb_per_env, const so101_color_out* out, float* depth, int* seg, void* stream) {
   REQUIRE_BOUND(s);
   RenderCams rc{};
   ShadeParams sp{};
-  if (!render_arguments(s, "so101_render_color", cams, ncam, height, width, n_render, s->n_envs, env_index != nullptr, true, NDYN - 1, rc)) return SO101_ERR_ARG;
-  if (!shade_arguments(s, "so101_render_color", shading, geom_rgb, out, sp)) return SO101_ERR_ARG;
+  if (!render_arguments(s, api, cams, ncam, height, width, n_render, s->n_envs, env_index != nullptr, color || depth || seg, NDYN - 1, rc)) return SO101_ERR_ARG;
+  if (color && !shade_arguments(s, api, shading, geom_rgb, out, sp)) return SO101_ERR_ARG;
   RenderHost& R = s->render;
-  if (R.has_meshes() && !R.planes_set) { s->err = "so101_render_color: the scene has mesh geoms and no hull planes (call so101_set_hull_planes)"; return SO101_ERR_STATE; }
+  if (R.has_meshes() && !R.planes_set) { s->err = std::string(api) + ": the scene has mesh geoms and no hull planes (call so101_set_hull_planes)"; return SO101_ERR_STATE; }
   GUARD_DEVICE(s);
   const size_t cap = R.cap, px_bytes = R.pixel_bytes();
-  const bool shade = out->rgb || out->normal;
-  const bool grown = R.reserve(s, (size_t)n_render) && (!shade || (out->depth && out->seg) || R.reserve_pixels(s, (size_t)n_render * ncam * height * width));
+  const bool shade = color && (out->rgb || out->normal);
+  if (color) { depth = out->depth; seg = (int*)out->seg; }
+  // (the pixel scratch: k_shade reads the depth and seg k_render wrote, so a caller who asks for neither gets them there)
+  const bool grown = R.reserve(s, (size_t)n_render) && (!shade || (depth && seg) || R.reserve_pixels(s, (size_t)n_render * ncam * height * width));
   s->scratch_bytes += R.frame_bytes() * R.cap - R.frame_bytes() * cap;          // (the scratch it had is gone when the growth failed)
   s->scratch_bytes += R.pixel_bytes() - px_bytes;
   if (!grown) return SO101_ERR_HIP;
-  float* depth = out->depth ? out->depth : (shade ? R.px_depth : nullptr);
-  int* seg = out->seg ? (int*)out->seg : (shade ? R.px_seg : nullptr);
+  if (shade && !depth) depth = R.px_depth;
+  if (shade && !seg) seg = R.px_seg;
   so101::launch_render(n_render, (hipStream_t)stream, s->dm, make_params(s), s->buf, (const int*)env_index, rc, ncam, height, width,
                        R.hull_planes, R.plane_adr, R.frames, R.cams, depth, seg);
   LAUNCH_CHECK(s, "k_render");
@@ -812,6 +731,16 @@ int so101_render_color(so101_sim* s, const so101_camera* cams, int ncam, int hei
     LAUNCH_CHECK(s, "k_shade");
   }
   return SO101_OK;
+}
+
+int so101_render(so101_sim* s, const so101_camera* cams, int ncam, int height, int width, const int32_t* env_index, int n_render,
+                 float* depth, int32_t* seg, void* stream) {
+  return render_call(s, "so101_render", false, cams, ncam, height, width, env_index, n_render, nullptr, nullptr, 0, nullptr, depth, (int*)seg, stream);
+}
+
+int so101_render_color(so101_sim* s, const so101_camera* cams, int ncam, int height, int width, const int32_t* env_index, int n_render,
+                       const so101_shading* shading, const float* geom_rgb, int rgb_per_env, const so101_color_out* out, void* stream) {
+  return render_call(s, "so101_render_color", true, cams, ncam, height, width, env_index, n_render, shading, geom_rgb, rgb_per_env, out, nullptr, nullptr, stream);
 }
 
 // ---- Cartesian tool control (csrc/so101_tool_chain.hpp)
@@ -924,14 +853,7 @@ int so101_proximity(so101_sim* s, const int32_t* env_index, int n, const float* 
                     const so101_proximity_out* out, void* stream) {
   if (!s) return SO101_ERR_ARG;
   const so101_proximity_out* o = out;
-  const char* bad = nullptr;
-  if (!o) bad = "NULL out";
-  else if (!o->dist && !o->geom && !o->point && !o->normal && !o->flags && !o->queries) bad = "no output (every pointer of out is NULL)";
-  else if (n < 1 || n > (1 << 26)) bad = "n must be 1 .. 2^26";
-  else if (!env_index && n > s->n_envs) bad = "n exceeds the envs of the handle";
-  else if (npair < 1 || npair > SO101_TOUCH_MAX_PAIRS) bad = "npair must be 1 .. 16";
-  else if (!pairs) bad = "NULL pairs";
-  if (bad) { s->err = std::string("so101_proximity: ") + bad; return SO101_ERR_ARG; }
+  if (int rc = check_proximity_arguments(s, "so101_proximity", o, env_index != nullptr, n, s->n_envs, pairs != nullptr, npair)) return rc;          // (so101_host.hpp)
   const int ngeom = s->hm.ngeom;
   if (ngeom > 128) { s->err = "so101_proximity: the model has more than 128 geoms (a group mask has 128 bits)"; return SO101_ERR_STATE; }
   TouchPairsT<4> T{};

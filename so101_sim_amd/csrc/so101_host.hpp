@@ -9,6 +9,7 @@
 #include "so101_tables.hpp"
 #include "so101_tool_chain.hpp"
 #include "so101_contact_report.hpp"
+#include "so101_step_plan.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -435,6 +436,19 @@ inline int check_contact_arguments(HostHandle* s, const char* api, const so101_c
   else if (npair > 0 && !has_pairs) bad = "NULL pairs with npair > 0";
   else if (npair == 0 && (o->pair_count || o->pair_dist || o->pair_normal || o->pair_force)) bad = "a pair output with npair == 0";
   else if (!forces && (o->force || o->pair_normal || o->pair_force)) bad = "force, pair_normal and pair_force need forces != 0";
+  if (bad) { s->err = std::string(api) + ": " + bad; return SO101_ERR_ARG; }
+  return SO101_OK;
+}
+
+// the same for so101_proximity and so101_tree_proximity: the outputs, the count and the pair arguments
+inline int check_proximity_arguments(HostHandle* s, const char* api, const so101_proximity_out* o, bool has_index, int n, int n_envs, bool has_pairs, int npair) {
+  const char* bad = nullptr;
+  if (!o) bad = "NULL out";
+  else if (!o->dist && !o->geom && !o->point && !o->normal && !o->flags && !o->queries) bad = "no output (every pointer of out is NULL)";
+  else if (n < 1 || n > (1 << 26)) bad = "n must be 1 .. 2^26";
+  else if (!has_index && n > n_envs) bad = "n exceeds the envs of the handle";
+  else if (npair < 1 || npair > SO101_TOUCH_MAX_PAIRS) bad = "npair must be 1 .. 16";
+  else if (!has_pairs) bad = "NULL pairs";
   if (bad) { s->err = std::string(api) + ": " + bad; return SO101_ERR_ARG; }
   return SO101_OK;
 }

@@ -260,12 +260,7 @@ struct ChainQueues {
 enum { CS_T_POP = 0, CS_T_IDLE, CS_T_NARROW, CS_T_SOLVE, CS_N_NARROW, CS_N_SOLVE, CS_N_IDLE, CS_WAVES, CS_T_LIFE, CS_N };
 struct SolveIO { float* obs; float* reward; float* discount; unsigned char* step_type; unsigned char* need_reset; int* diag; };
 #define STATE_AOS 64
-#ifndef NARROW_CHUNK
-#define NARROW_CHUNK 4     // candidate pairs per narrowphase work item
-#endif
-#ifndef SO101_LIST_ROWS_DEFAULT
-#define SO101_LIST_ROWS_DEFAULT 1     // k_narrow<false>'s list row pass where SO101_NARROW_LIST_ROWS is unset (so101_hip.hip; measurements: profiles/README.md)
-#endif
+#include "so101_step_plan.hpp"     // NARROW_CHUNK (candidate pairs per narrowphase work item) and SO101_LIST_ROWS_DEFAULT: the launch plan reads them too
 #define Q_NARROW 0        // queue index = type + class
 #define Q_SOLVE 2
 

@@ -22,9 +22,10 @@ struct TreeHandle : HostHandle {      // (so101_host.hpp: device, owned allocati
   TreePipe pipe{};
   bool pipeline = false;
   static constexpr int MAXSLICES = 4;
+  static_assert(MAXSLICES <= STEP_PLAN_MAX_SLICES, "a TreeStepPlan holds STEP_PLAN_MAX_SLICES slices");
   StreamLanes<MAXSLICES> slices;       // env slices whose chains overlap (one's narrowphase beside another's solve)
   RenderHost render;                   // cameras (so101_tree_set_hull_planes / so101_tree_render; so101_host.hpp)
-  int plan[4] = {0, 0, 0, 0};          // what the last so101_tree_step enqueued: env slices, kernel launches, memsets, path (0 none yet, 1 single kernel, 2 launch chain)
+  int plan[4] = {0, 0, 0, 0};          // what the last so101_tree_step that was enqueued whole launched, counted call by call: env slices, kernel launches, memsets, path (0 none yet, 1 single kernel, 2 launch chain)
 };
 
 namespace {

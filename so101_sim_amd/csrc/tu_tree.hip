@@ -26,6 +26,44 @@
 #include "so101_tree_host.hpp"
 
 namespace TREE_NS {
+namespace {
+// ---- cameras and colour cameras (k_tree_render_frames, then the library's one k_render through so101::launch_render_image)
+// One body for render and render_color (so101_shade.hpp): the depth / seg call is the colour call without shading.  k_tree_render_frames and the
+// library's k_render, then - shading asked for - its one k_shade through so101::launch_shade_image.  color: the colour call (outputs in `out`, else
+// depth and seg)
+int tree_render_call(TreeHandle* s, const std::string& api, bool color, const so101_camera* cams, int ncam, int height, int width, const int32_t* env_index, int n_render,
+                            int source, const so101_shading* shading, const float* geom_rgb, int rgb_per_env, const so101_color_out* out, float* depth, int* seg, void* stream) {
+  if (!s) return SO101_ERR_ARG;
+  RenderCams rc{};
+  ShadeParams sp{};
+  if (!render_arguments(s, api.c_str(), cams, ncam, height, width, n_render, s->n_envs, env_index != nullptr, color || depth || seg, s->hm.nbody - 1, rc)) return SO101_ERR_ARG;
+  if (source != 0 && source != 1) { s->err = api + ": source must be 0 (the bound qpos) or 1 (the delayed physics-state line)"; return SO101_ERR_ARG; }
+  if (color && !shade_arguments(s, api.c_str(), shading, geom_rgb, out, sp)) return SO101_ERR_ARG;
+  RenderHost& R = s->render;
+  if (R.has_meshes() && !R.planes_set) { s->err = api + ": the scene has mesh geoms and no hull planes (call so101_tree_set_hull_planes)"; return SO101_ERR_STATE; }
+  if (source == 0 && !s->bound) { s->err = api + " before so101_tree_bind_state"; return SO101_ERR_STATE; }
+  if (source == 1 && !s->env.ps_delayed) { s->err = api + ": source 1 needs the physics-state line (so101_tree_bind_physics_state)"; return SO101_ERR_STATE; }
+  GUARD_DEVICE(s);
+  const bool shade = color && (out->rgb || out->normal);
+  if (color) { depth = out->depth; seg = (int*)out->seg; }
+  if (!R.reserve(s, (size_t)n_render)) return SO101_ERR_HIP;
+  // (the pixel scratch: k_shade reads the depth and seg k_render wrote, so a caller who asks for neither gets them there)
+  if (shade && !(depth && seg) && !R.reserve_pixels(s, (size_t)n_render * ncam * height * width)) return SO101_ERR_HIP;
+  if (shade && !depth) depth = R.px_depth;
+  if (shade && !seg) seg = R.px_seg;
+  const float* q = source == 0 ? s->buf.qpos : s->env.ps_delayed;
+  const size_t lane_stride = source == 0 ? (size_t)s->n_envs : 1, env_stride = source == 0 ? 1 : (size_t)(s->hm.nq + s->hm.nv);
+  hipLaunchKernelGGL(k_tree_render_frames, dim3(n_render), dim3(64), 0, (hipStream_t)stream, s->dm, s->dg, q, lane_stride, env_stride, s->n_envs, (const int*)env_index, rc, ncam,
+                     R.frames, R.cams);
+  so101::launch_render_image(n_render, (hipStream_t)stream, s->dg, R.frames, R.cams, R.hull_planes, R.plane_adr, ncam, height, width, depth, seg);
+  if (!hip_ok(s, hipGetLastError(), "k_render")) return SO101_ERR_HIP;
+  if (shade)
+    so101::launch_shade_image(n_render, (hipStream_t)stream, s->dg, R.frames, R.cams, R.hull_planes, R.plane_adr, ncam, height, width, depth, seg, geom_rgb, rgb_per_env != 0,
+                              (const int*)env_index, sp, out->rgb, out->normal);
+  return hip_ok(s, hipGetLastError(), "k_shade") ? SO101_OK : SO101_ERR_HIP;
+}
+}  // namespace
+
 extern "C" {
 
 int TAPI(create)(const void* blob, size_t bytes, int n_envs, int hip_device, TreeHandle** out) {
@@ -183,43 +221,46 @@ int TAPI(step)(TreeHandle* s, const float* action, float* obs, float* reward, fl
   hipStream_t st = (hipStream_t)stream;
   TreeTask T = task_now(s);
   const bool post = T.reward_mode != 0;          // contact rewards: one more narrowphase launch, on the post-step state
-  if (s->pipeline && s->pipe.pose && T.n_substeps + (post ? 1 : 0) <= TPIPE_MAXSUB) {
+  // what to launch is decided by the plan (so101_step_plan.hpp); this function executes it and counts what it enqueued
+  const TreeStepPlan plan = plan_tree_step(s->n_envs, T.n_substeps, post, s->pipeline && s->pipe.pose, TreeHandle::MAXSLICES, TPIPE_MAXSUB, read_step_knobs());
+  int launches = 0, memsets = 0;
+  if (plan.chain) {
     // launch chain: prologue, then per substep the narrowphase of every candidate pair of the batch and the rest of the substep per env.
     // Env slices on their own streams: the narrowphase of one (latency-bound, two wavefronts per SIMD) runs beside the solve of another
-    // (four envs per CU by its LDS footprint); the slices share nothing but the model.  Measured, 1 / 2 / 3 / 4 slices:
-    // ALOHA (4096 envs) 206 / 232 / 228 / 231 k, Dining (1024 envs) 33.2 / 44.6 / - / 47.0 k env-steps/s.
-    static const int slices_env = getenv("SO101_TREE_SLICES") ? atoi(getenv("SO101_TREE_SLICES")) : 0;          // (kernel experiments)
-    const int G = s->n_envs < 128 ? 1 : (slices_env >= 1 && slices_env <= TreeHandle::MAXSLICES ? slices_env : (s->n_envs < 512 ? 2 : 4));
-    if (!s->slices.fork(s, st, G)) return SO101_ERR_HIP;
-    s->plan[0] = G; s->plan[1] = G * (1 + 2 * T.n_substeps + (post ? 2 : 0)); s->plan[2] = G; s->plan[3] = 2;
-    for (int g = 0; g < G; g++) {
-      int e0 = (int)((long long)s->n_envs * g / G), ng = (int)((long long)s->n_envs * (g + 1) / G) - e0;
+    // (four envs per CU by its LDS footprint); the slices share nothing but the model.
+    if (!s->slices.fork(s, st, plan.G)) return SO101_ERR_HIP;
+    for (int g = 0; g < plan.G; g++) {
+      const int e0 = plan.slice[g].e0, ng = plan.slice[g].ng, nw = plan.slice[g].nw;
       TreePipe P = s->pipe;
       P.counters = s->pipe.counters + 2 * TPIPE_MAXSUB * g;
       P.work = s->pipe.work + (size_t)2 * e0 * TCAND;
       P.work_cap = (unsigned int)ng * TCAND;
-      static const int nwq_env = getenv("SO101_TREE_NARROW_WAVES_Q") ? atoi(getenv("SO101_TREE_NARROW_WAVES_Q")) : 0;      // (kernel experiments: quarter waves per env)
-      int nw = (int)((long long)ng * (nwq_env > 0 ? nwq_env : 8) / 4); nw = nw < 1 ? 1 : (nw < 4096 ? nw : 4096);
       hipStream_t gs;
       if (!s->slices.stream_of(s, g, &gs)) return SO101_ERR_HIP;
       if (!hip_ok(s, hipMemsetAsync(P.counters, 0, 2 * TPIPE_MAXSUB * sizeof(int), gs), "hipMemsetAsync(pipeline)")) return SO101_ERR_HIP;
+      memsets++;
       hipLaunchKernelGGL(k_tree_pipe_begin, dim3(ng), dim3(64), 0, gs, s->dm, s->dg, T, s->buf, s->env, store_now(s), P, action, obs, reward, discount, step_type, e0);
+      launches++;
       for (int k = 0; k < T.n_substeps; k++) {
         hipLaunchKernelGGL(k_tree_narrow, dim3(nw), dim3(64), 0, gs, s->dm, s->dg, P, s->n_envs, k);
         hipLaunchKernelGGL(k_tree_pipe_solve, dim3(ng), dim3(64), 0, gs, s->dm, s->dg, T, s->buf, s->env, P, k, (int)(!post && k == T.n_substeps - 1), obs, reward, discount, step_type, e0);
+        launches += 2;
       }
       if (post) {
         hipLaunchKernelGGL(k_tree_narrow, dim3(nw), dim3(64), 0, gs, s->dm, s->dg, P, s->n_envs, T.n_substeps);
         hipLaunchKernelGGL(k_tree_pipe_finish, dim3(ng), dim3(64), 0, gs, s->dm, s->dg, T, s->buf, s->env, P, obs, reward, discount, step_type, e0);
+        launches += 2;
       }
       if (!hip_ok(s, hipGetLastError(), "k_tree_pipe_solve")) return SO101_ERR_HIP;
       if (!s->slices.join(s, g)) return SO101_ERR_HIP;
     }
   } else {
-    s->plan[0] = 1; s->plan[1] = 1; s->plan[2] = 0; s->plan[3] = 1;
     hipLaunchKernelGGL(k_tree_step, dim3(s->n_envs), dim3(64), 0, st, s->dm, s->dg, T, s->buf, s->env, store_now(s), action, obs, reward, discount, step_type);
+    launches++;
     if (!hip_ok(s, hipGetLastError(), "k_tree_step")) return SO101_ERR_HIP;
   }
+  // (a step that failed above leaves the plan of the last step that was enqueued whole)
+  s->plan[0] = plan.G; s->plan[1] = launches; s->plan[2] = memsets; s->plan[3] = plan.chain ? 2 : 1;
   launch_tree_prepare(s, (hipStream_t)stream);
   return SO101_OK;
 }
@@ -260,7 +301,7 @@ int TAPI(begin_episode)(TreeHandle* s, void* stream) {
   return hip_ok(s, hipGetLastError(), "k_tree_begin") ? SO101_OK : SO101_ERR_HIP;
 }
 
-// ---- cameras (k_tree_render_frames above, then the library's one k_render through so101::launch_render_image)
+// ---- cameras and colour cameras (tree_render_call above)
 int TAPI(set_hull_planes)(TreeHandle* s, const float* planes, const int32_t* plane_adr) {
   if (!s) return SO101_ERR_ARG;
   if (!planes || !plane_adr) { s->err = "so101_tree_set_hull_planes: NULL argument"; return SO101_ERR_ARG; }
@@ -271,53 +312,12 @@ int TAPI(set_hull_planes)(TreeHandle* s, const float* planes, const int32_t* pla
 
 int TAPI(render)(TreeHandle* s, const so101_camera* cams, int ncam, int height, int width, const int32_t* env_index, int n_render, int source,
                  float* depth, int32_t* seg, void* stream) {
-  if (!s) return SO101_ERR_ARG;
-  RenderCams rc{};
-  if (!render_arguments(s, "so101_tree_render", cams, ncam, height, width, n_render, s->n_envs, env_index != nullptr, depth || seg, s->hm.nbody - 1, rc)) return SO101_ERR_ARG;
-  if (source != 0 && source != 1) { s->err = "so101_tree_render: source must be 0 (the bound qpos) or 1 (the delayed physics-state line)"; return SO101_ERR_ARG; }
-  RenderHost& R = s->render;
-  if (R.has_meshes() && !R.planes_set) { s->err = "so101_tree_render: the scene has mesh geoms and no hull planes (call so101_tree_set_hull_planes)"; return SO101_ERR_STATE; }
-  if (source == 0 && !s->bound) { s->err = "so101_tree_render before so101_tree_bind_state"; return SO101_ERR_STATE; }
-  if (source == 1 && !s->env.ps_delayed) { s->err = "so101_tree_render: source 1 needs the physics-state line (so101_tree_bind_physics_state)"; return SO101_ERR_STATE; }
-  GUARD_DEVICE(s);
-  if (!R.reserve(s, (size_t)n_render)) return SO101_ERR_HIP;
-  const float* q = source == 0 ? s->buf.qpos : s->env.ps_delayed;
-  const size_t lane_stride = source == 0 ? (size_t)s->n_envs : 1, env_stride = source == 0 ? 1 : (size_t)(s->hm.nq + s->hm.nv);
-  hipLaunchKernelGGL(k_tree_render_frames, dim3(n_render), dim3(64), 0, (hipStream_t)stream, s->dm, s->dg, q, lane_stride, env_stride, s->n_envs, (const int*)env_index, rc, ncam,
-                     R.frames, R.cams);
-  so101::launch_render_image(n_render, (hipStream_t)stream, s->dg, R.frames, R.cams, R.hull_planes, R.plane_adr, ncam, height, width, depth, (int*)seg);
-  return hip_ok(s, hipGetLastError(), "k_render") ? SO101_OK : SO101_ERR_HIP;
+  return tree_render_call(s, "so101_tree_render", false, cams, ncam, height, width, env_index, n_render, source, nullptr, nullptr, 0, nullptr, depth, (int*)seg, stream);
 }
 
-// ---- colour cameras (so101_shade.hpp): the two kernels of render above, then the library's one k_shade through so101::launch_shade_image
 int TAPI(render_color)(TreeHandle* s, const so101_camera* cams, int ncam, int height, int width, const int32_t* env_index, int n_render, int source,
                        const so101_shading* shading, const float* geom_rgb, int rgb_per_env, const so101_color_out* out, void* stream) {
-  if (!s) return SO101_ERR_ARG;
-  RenderCams rc{};
-  ShadeParams sp{};
-  if (!render_arguments(s, "so101_tree_render_color", cams, ncam, height, width, n_render, s->n_envs, env_index != nullptr, true, s->hm.nbody - 1, rc)) return SO101_ERR_ARG;
-  if (source != 0 && source != 1) { s->err = "so101_tree_render_color: source must be 0 (the bound qpos) or 1 (the delayed physics-state line)"; return SO101_ERR_ARG; }
-  if (!shade_arguments(s, "so101_tree_render_color", shading, geom_rgb, out, sp)) return SO101_ERR_ARG;
-  RenderHost& R = s->render;
-  if (R.has_meshes() && !R.planes_set) { s->err = "so101_tree_render_color: the scene has mesh geoms and no hull planes (call so101_tree_set_hull_planes)"; return SO101_ERR_STATE; }
-  if (source == 0 && !s->bound) { s->err = "so101_tree_render_color before so101_tree_bind_state"; return SO101_ERR_STATE; }
-  if (source == 1 && !s->env.ps_delayed) { s->err = "so101_tree_render_color: source 1 needs the physics-state line (so101_tree_bind_physics_state)"; return SO101_ERR_STATE; }
-  GUARD_DEVICE(s);
-  const bool shade = out->rgb || out->normal;
-  if (!R.reserve(s, (size_t)n_render)) return SO101_ERR_HIP;
-  if (shade && !(out->depth && out->seg) && !R.reserve_pixels(s, (size_t)n_render * ncam * height * width)) return SO101_ERR_HIP;
-  float* depth = out->depth ? out->depth : (shade ? R.px_depth : nullptr);
-  int* seg = out->seg ? (int*)out->seg : (shade ? R.px_seg : nullptr);
-  const float* q = source == 0 ? s->buf.qpos : s->env.ps_delayed;
-  const size_t lane_stride = source == 0 ? (size_t)s->n_envs : 1, env_stride = source == 0 ? 1 : (size_t)(s->hm.nq + s->hm.nv);
-  hipLaunchKernelGGL(k_tree_render_frames, dim3(n_render), dim3(64), 0, (hipStream_t)stream, s->dm, s->dg, q, lane_stride, env_stride, s->n_envs, (const int*)env_index, rc, ncam,
-                     R.frames, R.cams);
-  so101::launch_render_image(n_render, (hipStream_t)stream, s->dg, R.frames, R.cams, R.hull_planes, R.plane_adr, ncam, height, width, depth, seg);
-  if (!hip_ok(s, hipGetLastError(), "k_render")) return SO101_ERR_HIP;
-  if (shade)
-    so101::launch_shade_image(n_render, (hipStream_t)stream, s->dg, R.frames, R.cams, R.hull_planes, R.plane_adr, ncam, height, width, depth, seg, geom_rgb, rgb_per_env != 0,
-                              (const int*)env_index, sp, out->rgb, out->normal);
-  return hip_ok(s, hipGetLastError(), "k_shade") ? SO101_OK : SO101_ERR_HIP;
+  return tree_render_call(s, "so101_tree_render_color", true, cams, ncam, height, width, env_index, n_render, source, shading, geom_rgb, rgb_per_env, out, nullptr, nullptr, stream);
 }
 
 // ---- Cartesian tool control (so101_tool_chain.hpp)
@@ -404,18 +404,12 @@ int TAPI(proximity)(TreeHandle* s, const int32_t* env_index, int n, const float*
                     const so101_proximity_out* out, void* stream) {
   if (!s) return SO101_ERR_ARG;
   const so101_proximity_out* o = out;
-  const char* bad = nullptr;
-  if (!o) bad = "NULL out";
-  else if (!o->dist && !o->geom && !o->point && !o->normal && !o->flags && !o->queries) bad = "no output (every pointer of out is NULL)";
-  else if (n < 1 || n > (1 << 26)) bad = "n must be 1 .. 2^26";
-  else if (!env_index && n > s->n_envs) bad = "n exceeds the envs of the handle";
-  else if (npair < 1 || npair > SO101_TOUCH_MAX_PAIRS) bad = "npair must be 1 .. 16";
-  else if (!pairs) bad = "NULL pairs";
-  if (bad) { s->err = std::string("so101_tree_proximity: ") + bad; return SO101_ERR_ARG; }
+  if (int rc = check_proximity_arguments(s, "so101_tree_proximity", o, env_index != nullptr, n, s->n_envs, pairs != nullptr, npair)) return rc;          // (so101_host.hpp)
   TouchPairsT<8> T{};
   if (int rc = pack_touch_pairs(s, "so101_tree_proximity", pairs, npair, s->hm.ngeom, T)) return rc;
   if (!(std::isfinite(max_dist) && max_dist > 0.f && max_dist <= 10.f)) { s->err = "so101_tree_proximity: max_dist must be a finite number above 0 and at most 10"; return SO101_ERR_ARG; }
   ProxCols C{};
+  const char* bad = nullptr;
   if (q && !q_adr) bad = "q without q_adr";
   else if (!q && q_adr) bad = "q_adr without q";
   else if (q && (ncol < 1 || ncol > PROX_MAXCOL)) bad = "ncol must be 1 .. 16";

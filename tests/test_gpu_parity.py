@@ -85,6 +85,17 @@ def test_settled_store_is_bit_identical(make_sim, prefetch):
 
 def test_pipelined_step_matches_fused(make_sim, golden):
     pc.check_pipeline_identical(make_sim, golden, n=8, steps=6)
+    # 66 envs in four chains: four UNEQUAL slices (16, 17, 16, 17 envs) in the plain sorted order, no dealing out - the plan of
+    # tests/test_step_plan.py's table that no other size here steps.  groups=4 is what groups=0 picks with six hardware queues or more;
+    # asked for explicitly, the case does not depend on how many queues the process was started with.
+    sims = []
+
+    def make(n, **cfg):
+        sims.append(make_sim(n, **cfg))
+        return sims[-1]
+    pc.check_pipeline_identical(make, golden, n=66, steps=3, all_reset_last=False, pipelines=(0, 1), groups=4)
+    info = sims[-1].sim.info()
+    assert info["step_path"] == 1 and info["chains"] == 4 and info["narrow_list_rows"] == 0, info
 
 
 @pytest.mark.parametrize("n,steps", [(8, 6), (512, 4)])

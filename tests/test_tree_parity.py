@@ -567,6 +567,19 @@ def test_launch_chain_slices_are_bit_identical(scene, n):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("n,reward_mode,plan", [(128, 0, (2, 42, 2, 2)), (64, 0, (1, 21, 1, 2)), (128, 1, (2, 46, 2, 2))])
+def test_launch_chain_plan_is_counted_as_enqueued(n, reward_mode, plan):
+    """so101_tree_last_plan after one pipelined step on the hand-over blob: slices, kernel launches and memsets as the step function counted
+    them while it enqueued them - the values of the closed form the library held before it counted (tests/test_step_plan.py has the table);
+    a contact reward ends every slice's chain with one more narrowphase launch and k_tree_pipe_finish."""
+    sim = TreeArraySim(_blobs("banana")[1], n, backend="gpu")
+    assert sim.sim.last_plan() == (0, 0, 0, 0)
+    sim.enable_env(seed=5, last_step=3, settle_max_substeps=20, pipeline=1, n_substeps=10, reward_mode=reward_mode)
+    sim.step(np.tile(np.concatenate([scenes.ALOHA_HOME_CTRL] * 2), (n, 1)))
+    assert sim.sim.last_plan() == plan
+
+
+@pytest.mark.gpu
 def test_settled_store_of_the_tree_engine_is_bit_identical():
     """compute_settled(): the settle results of the first episodes of every env, computed ahead of time; the resets that find them copy -
     the rollout across two auto-resets is bit-identical to the one that settles inside the step calls."""
