@@ -27,21 +27,16 @@ aloha2_task.py:153-159: whole control steps, handed to the kernels by so101_tree
 from __future__ import annotations
 
 import collections
-import os
 
 import numpy as np
 
 from . import native
 from ._dmenv import Array, BoundedArray, TimeStep
-from .model import blob as blobfmt
 from .model import scenes
 from . import appearance as _appearance
 from . import contacts as _contacts
-from .proximity import ProximitySensing
-from .tool_control import ToolControl
+from ._env_base import DEFAULT_CONTROL_TIMESTEP, PHYSICS_TIMESTEP, SETTLE_WARNING, EnvironmentBase, generator_of, pop_task_keywords
 
-DEFAULT_CONTROL_TIMESTEP = 0.02
-PHYSICS_TIMESTEP = 0.002
 DEFAULT_JOINTS_DELAY_SECS, DEFAULT_PHYSICS_DELAY_SECS = 0.1, 0.3          # aloha2_task.py:102-103
 NPOS, NVEL = 14, 16
 
@@ -59,10 +54,14 @@ class HandOverTask:
         self.object_name = object_name
         self.reward_based_on_overlap = bool(reward_based_on_overlap)         # False: the contact sequence of hand_over.py:286-338
         self.reward_requires_handover = bool(reward_requires_handover)       # (read by the contact-sequence mode only, as in the reference)
-        self.control_timestep = float(kwargs.pop("control_timestep", DEFAULT_CONTROL_TIMESTEP))
-        self.cameras = tuple(kwargs.pop("cameras", ()))
-        self.image_observation_enabled = bool(kwargs.pop("image_observation_enabled", True))
-        self.terminate_episode = bool(kwargs.pop("terminate_episode", True))
+        self._pop_keywords(kwargs)
+        self._instruction = scenes.ALOHA_INSTRUCTIONS[object_name]
+
+    scene = "hand_over"
+
+    def _pop_keywords(self, kwargs):
+        """the keywords of AlohaTask (aloha2_task.py:145-160), shared by the tasks on it"""
+        pop_task_keywords(self, kwargs)
         self.waist_joint_limit = float(kwargs.pop("waist_joint_limit", np.pi / 2))
         if float(kwargs.pop("table_height_offset", scenes.ALOHA_TABLE_HEIGHT_OFFSET)) != scenes.ALOHA_TABLE_HEIGHT_OFFSET:
             raise NotImplementedError("the model blob is compiled for table_height_offset = 0.011 (aloha2_task.py:107)")
@@ -72,9 +71,6 @@ class HandOverTask:
         self.image_observation_delay_secs = float(kwargs.pop("image_observation_delay_secs", DEFAULT_PHYSICS_DELAY_SECS))
         self.joints_delay_steps = self._delay_steps(self.joints_observation_delay_secs, "joints_observation_delay_secs")
         self.physics_delay_steps = self._delay_steps(self.image_observation_delay_secs, "image_observation_delay_secs")
-        self._instruction = scenes.ALOHA_INSTRUCTIONS[object_name]
-
-    scene = "hand_over"
 
     def load_blob(self, real: str):
         return scenes.load_aloha_blob(self.object_name, real)
@@ -111,17 +107,7 @@ class DiningPlaceInContainerTask(HandOverTask):
         self.reward_type = cfg["reward"]
         self.reward_based_on_overlap = cfg["reward"] == "bbox"
         self.reward_requires_handover = False
-        self.control_timestep = float(kwargs.pop("control_timestep", DEFAULT_CONTROL_TIMESTEP))
-        self.cameras = tuple(kwargs.pop("cameras", ()))
-        self.image_observation_enabled = bool(kwargs.pop("image_observation_enabled", True))
-        self.terminate_episode = bool(kwargs.pop("terminate_episode", True))
-        self.waist_joint_limit = float(kwargs.pop("waist_joint_limit", np.pi / 2))
-        if float(kwargs.pop("table_height_offset", scenes.ALOHA_TABLE_HEIGHT_OFFSET)) != scenes.ALOHA_TABLE_HEIGHT_OFFSET:
-            raise NotImplementedError("the model blob is compiled for table_height_offset = 0.011 (aloha2_task.py:107)")
-        self.joints_observation_delay_secs = float(kwargs.pop("joints_observation_delay_secs", DEFAULT_JOINTS_DELAY_SECS))
-        self.image_observation_delay_secs = float(kwargs.pop("image_observation_delay_secs", DEFAULT_PHYSICS_DELAY_SECS))
-        self.joints_delay_steps = self._delay_steps(self.joints_observation_delay_secs, "joints_observation_delay_secs")
-        self.physics_delay_steps = self._delay_steps(self.image_observation_delay_secs, "image_observation_delay_secs")
+        self._pop_keywords(kwargs)
         self._instruction = cfg["instruction"]
 
     def load_blob(self, real: str):
@@ -143,55 +129,35 @@ def aloha_action_spec(ctrlrange: np.ndarray, waist_joint_limit: float = np.pi / 
     return BoundedArray((14,), np.float32, lo, hi)
 
 
-class AlohaEnvironment(ToolControl, _contacts.ContactSensing, ProximitySensing, _appearance.ColorCameras):
+class AlohaEnvironment(EnvironmentBase):
     def __init__(self, task: HandOverTask, n_envs: int = 1, time_limit: float = float("inf"), random_state=None, device=None,
                  env_id_base: int = 0, solver_iterations: int = 0, solver_tolerance: float = -1.0, settle_max_substeps: int = 1000,
                  physics_state: bool | None = None, seed_compatible: bool = True, narrowphase: str = "epa", prefetch_resets: bool = True, pipeline: bool = True):
-        import torch
-        if not torch.cuda.is_available():
-            raise RuntimeError("so101_sim_amd needs a ROCm GPU (MI355X): the step path has no CPU fallback")
-        self.torch = torch
-        self.task = task
-        self.n_envs = N = int(n_envs)
-        self.device = torch.device(device if device is not None else "cuda:0")
         # N = 1: the reference's placements come from np.random.RandomState(seed) inside dm_control's PropPlacers.  With
         # seed_compatible (default) a single env draws them from the same generator in the same order - object position (3 draws,
         # hand_over.py:36-40), object yaw (1, :41-49), container position (3 per attempt, <= 20 attempts against collisions, :51-56) -
         # and lets the kernels settle (so101_tree_settle).  Batches key the kernels' counter RNG by (seed, env id, episode) instead.
         self._seed_compatible = bool(seed_compatible) and int(n_envs) == 1
-        self._np_random = random_state if isinstance(random_state, np.random.RandomState) else (
-            np.random.RandomState() if random_state is None else np.random.RandomState(int(random_state)))
+        self._np_random = generator_of(random_state)
         self._pending_first = False
-        if isinstance(random_state, np.random.RandomState):
-            seed = 0 if self._seed_compatible else int(random_state.randint(0, 2**31 - 1))
-        elif random_state is None:
-            seed = int.from_bytes(os.urandom(4), "little")
-        else:
-            seed = int(random_state)
-        self.seed = seed
+        self._open_device(task, n_envs, device, random_state, host_draws=self._seed_compatible)
+        torch, seed, N = self.torch, self.seed, self.n_envs
         blob, self.meta = task.load_blob("f32")
-        m = blobfmt.unpack(blob)
+        m, m64 = self._model(), self._model("f64")      # (f64: the distributions' bounds unrounded: the draws must be the reference's, bit for bit)
         self._ctrlrange = np.asarray(m["act_ctrlrange"], dtype=np.float64).reshape(-1, 2)
-        con_body, obj_body = int(np.asarray(m["task_container_body"]).ravel()[0]), int(np.asarray(m["task_object_body"]).ravel()[0])
         qadr = np.asarray(m["body_qposadr"])
-        m64 = blobfmt.unpack(task.load_blob("f64")[0])      # (the distributions' bounds unrounded: the draws must be the reference's, bit for bit)
         if task.scene == "dining":
             self._dining = dict(lo=np.asarray(m64["task_region_lo"], dtype=np.float64).reshape(6, 3), hi=np.asarray(m64["task_region_hi"], dtype=np.float64).reshape(6, 3),
                                 qadr=[int(qadr[b]) for b in np.asarray(m["task_prop_bodies"]).ravel()])
-        self._placer = dict(obj_lo=np.asarray(m64["task_obj_pos_lo"], dtype=np.float64), obj_hi=np.asarray(m64["task_obj_pos_hi"], dtype=np.float64),
-                            yaw=np.asarray(m64["task_obj_yaw"], dtype=np.float64), con_lo=np.asarray(m64["task_con_pos_lo"], dtype=np.float64),
-                            con_hi=np.asarray(m64["task_con_pos_hi"], dtype=np.float64), qo=int(qadr[obj_body]), qc=int(qadr[con_body]),
-                            con_geoms=set(np.nonzero(np.asarray(m["geom_body"]) == con_body)[0].tolist()))
+        self._placer = dict(self._hand_over_placer(), qo=int(qadr[int(np.asarray(m["task_object_body"]).ravel()[0])]),
+                            qc=int(qadr[int(np.asarray(m["task_container_body"]).ravel()[0])]))
         with torch.cuda.device(self.device):
-            if narrowphase not in ("mpr", "epa"):
-                raise ValueError(f"narrowphase must be 'mpr' or 'epa', got {narrowphase!r}")
-            from . import build as _build
-            self.narrowphase = narrowphase       # "mpr": the -DSO101_MPR build of the library, built on demand (env.py)
-            self.sim = native.TreeSim(blob, N, device=self.device.index or 0, lib_path=_build.build(mpr=True) if narrowphase == "mpr" else None)
+            # "mpr": the -DSO101_MPR build of the library, built on demand
+            self.sim = native.TreeSim(blob, N, device=self.device.index or 0, lib_path=self._narrowphase_library(narrowphase))
         s = self.sim
         if (s.nu, s.obs_dim) != (NPOS, 3 * NPOS + 2 * NVEL):
             raise RuntimeError("unexpected model dimensions for an ALOHA scene")
-        z = lambda *sh, dt=torch.float32: torch.zeros(*sh, dtype=dt, device=self.device)
+        z = self._zeros
         self.qpos, self.qvel, self.ctrl, self.warm = z(s.nq, N), z(s.nv, N), z(s.nu, N), z(s.nv, N)
         jd, pd = task.joints_delay_steps, task.physics_delay_steps
         self._ring_pos, self._ring_vel = z(max(jd, 1), NPOS, N), z(max(jd, 1), NVEL, N)
@@ -220,11 +186,8 @@ class AlohaEnvironment(ToolControl, _contacts.ContactSensing, ProximitySensing, 
         # for batches they are opt-in (58 + 58 floats per env and step).
         self._with_state = bool(task.image_observation_enabled if physics_state is None and N == 1 else physics_state)
         self._ps_dim = s.nq + s.nv
-        self.physics_state = self.delayed_physics_state = self._ps_ring = None
         if self._with_state:
-            self._ps_ring = z(max(pd, 1), self._ps_dim, N)
-            self.physics_state, self.delayed_physics_state = z(N, self._ps_dim), z(N, self._ps_dim)
-            s.bind_physics_state(self._ps_ring.data_ptr(), self.physics_state.data_ptr(), self.delayed_physics_state.data_ptr())
+            self._bind_physics_state(max(pd, 1), self._ps_dim)
 
     # ------------------------------------------------------------------ specs
     def action_spec(self) -> BoundedArray:
@@ -246,10 +209,13 @@ class AlohaEnvironment(ToolControl, _contacts.ContactSensing, ProximitySensing, 
             spec["delayed_physics_state"] = Array((self._ps_dim,), np.float64, "delayed_physics_state")
         return spec
 
-    # ------------------------------------------------------------------ stepping
-    def _stream(self):
-        return self.torch.cuda.current_stream(self.device).cuda_stream
+    def _load_blob(self, real: str):
+        return self.task.load_blob(real)
 
+    def _debug_layout(self):
+        return self.sim.dbg, self.sim.debug_dim
+
+    # ------------------------------------------------------------------ stepping
     def _obs_dict(self):
         o = collections.OrderedDict()
         cut = lambda k: self.obs[:, _SLICES[k][0]:_SLICES[k][1]]
@@ -287,17 +253,6 @@ class AlohaEnvironment(ToolControl, _contacts.ContactSensing, ProximitySensing, 
             return TimeStep(st, float(self.reward[0]), float(self.discount[0]), obs)
         return TimeStep(self.step_type, self.reward, self.discount, obs)
 
-    def _container_collides(self) -> bool:
-        if not hasattr(self, "_dbg"):
-            self._dbg = self.torch.zeros(1, self.sim.debug_dim, device=self.device)
-        self.sim.debug_forward(self._dbg.data_ptr(), self._stream())
-        r = self._dbg[0].cpu().numpy()
-        D = self.sim.dbg
-        for k in range(int(r[D["COUNTS"]])):
-            if int(r[D["CON"] + 10 * k + 7]) in self._placer["con_geoms"] or int(r[D["CON"] + 10 * k + 8]) in self._placer["con_geoms"]:
-                return True
-        return False
-
     def _reset_seed_compatible_dining(self):
         """Dining._sample_props + the two PropPlacers (dining.py:162-267) with numpy's generator, in the reference's order: six region
         samples `uniform(low, high)` (top left / middle / right, bottom left / middle / right: three numbers each), `shuffle` of the top and
@@ -319,46 +274,30 @@ class AlohaEnvironment(ToolControl, _contacts.ContactSensing, ProximitySensing, 
             q[a + 3:a + 7] = [np.cos(0.5 * yaw), 0.0, 0.0, np.sin(0.5 * yaw)]
             yaws.append(float(yaw))
         self.ctrl.copy_(torch.as_tensor(np.concatenate([scenes.ALOHA_HOME_CTRL, scenes.ALOHA_HOME_CTRL]), dtype=torch.float32, device=self.device).unsqueeze(1))
-        self.qpos.copy_(torch.as_tensor(q, dtype=torch.float32, device=self.device).unsqueeze(1))
-        self.qvel.zero_(); self.warm.zero_()
+        self._write_state(q)
         self.placements = dict(zip(scenes.DINING_PLACER_ORDER, [dict(position=samples[regions[p]].copy(), yaw=yaws[p], region=int(regions[p])) for p in range(6)]))
         s.settle(self._stream())
         s.begin_episode(self._stream())
         self.episode += 1
         if int(self.diagnostics()[0, 4]) & 32:
             import warnings
-            warnings.warn("Failed to settle physics within the settle budget (dm_control warns likewise)")
+            warnings.warn(SETTLE_WARNING)
 
     def _reset_seed_compatible(self):
         """placements from numpy's generator in dm_control's PropPlacer order, settle and episode start by the kernels"""
         if self.task.scene == "dining":
             return self._reset_seed_compatible_dining()
-        torch, P, rs, s = self.torch, self._placer, self._np_random, self.sim
-        opos = rs.uniform(P["obj_lo"], P["obj_hi"])
-        yaw = rs.uniform(P["yaw"][0], P["yaw"][1])
+        torch, P, s = self.torch, self._placer, self.sim
         q = np.zeros(s.nq)
         q[:16] = np.concatenate([scenes.ALOHA_HOME_QPOS, scenes.ALOHA_HOME_QPOS])           # aloha2_task.py:374-377
-        q[P["qo"]:P["qo"] + 3] = opos
-        q[P["qo"] + 3:P["qo"] + 7] = [np.cos(0.5 * yaw), 0.0, 0.0, np.sin(0.5 * yaw)]
-        q[P["qc"] + 3] = 1.0
         self.ctrl.copy_(torch.as_tensor(np.concatenate([scenes.ALOHA_HOME_CTRL, scenes.ALOHA_HOME_CTRL]), dtype=torch.float32, device=self.device).unsqueeze(1))
-        placed = False
-        for _ in range(20):                                                                  # PropPlacer max_attempts_per_prop
-            q[P["qc"]:P["qc"] + 3] = rs.uniform(P["con_lo"], P["con_hi"])
-            self.qpos.copy_(torch.as_tensor(q, dtype=torch.float32, device=self.device).unsqueeze(1))
-            self.qvel.zero_(); self.warm.zero_()
-            if not self._container_collides():
-                placed = True
-                break
-        if not placed:
-            raise RuntimeError("Failed to place the container without collisions in 20 attempts (dm_control PropPlacer raises here too)")
-        self.placements = dict(object_position=opos.copy(), object_yaw=float(yaw), container_position=q[P["qc"]:P["qc"] + 3].copy())
+        self._place_hand_over(q, P["qo"], P["qc"])
         s.settle(self._stream())
         s.begin_episode(self._stream())
         self.episode += 1
         if int(self.diagnostics()[0, 4]) & 32:
             import warnings
-            warnings.warn("Failed to settle physics within the settle budget (dm_control warns likewise)")
+            warnings.warn(SETTLE_WARNING)
 
     def reset(self) -> TimeStep:
         """every env starts a new episode; returns FIRST"""
@@ -404,7 +343,7 @@ class AlohaEnvironment(ToolControl, _contacts.ContactSensing, ProximitySensing, 
         if self._seed_compatible:
             raise RuntimeError("a seed-compatible single env draws its placements from numpy's generator; nothing to precompute")
         torch, s, N = self.torch, self.sim, self.n_envs
-        z = lambda *sh, dt=torch.float32: torch.zeros(*sh, dtype=dt, device=self.device)
+        z = self._zeros
         self._store = (z(n_episodes, s.nq, N), z(n_episodes, s.nv, N), z(n_episodes, s.nv, N), z(n_episodes, N, dt=torch.int32))
         s.compute_settled(first_episode, n_episodes, *(t.data_ptr() for t in self._store), self._stream())
         self.torch.cuda.current_stream(self.device).synchronize()
@@ -412,23 +351,6 @@ class AlohaEnvironment(ToolControl, _contacts.ContactSensing, ProximitySensing, 
         return self._store
 
     # ------------------------------------------------------------------ depth / segmentation cameras (cameras.py)
-    def _ensure_hull_planes(self):
-        """Facet planes of the mesh geoms' hulls, computed from the blob's vertices and handed to the library on first use"""
-        if getattr(self, "_planes_set", False):
-            return
-        from .model import meshes
-        m = blobfmt.unpack(self.task.load_blob("f32")[0])
-        verts = np.asarray(m["mesh_vert"], dtype=np.float64).reshape(-1, 3)
-        adr, chunks = [0], []
-        for t, a, n in zip(m["geom_type"], m["geom_vertadr"], m["geom_vertnum"]):
-            if int(t) == 5:
-                chunks.append(meshes.hull_planes(verts[a:a + n]))
-            adr.append(adr[-1] + (len(chunks[-1]) if int(t) == 5 else 0))
-        planes = np.concatenate(chunks) if chunks else np.zeros((0, 4))
-        with self.torch.cuda.device(self.device):
-            self.sim.set_hull_planes(planes.astype(np.float32), np.asarray(adr, dtype=np.int32))
-        self._planes_set = True
-
     def render_depth(self, camera, height: int, width: int, env_ids=None, segmentation: bool = True, delayed: bool = False):
         """Depth and geom-id images of the collision geometry, by ray casting on the GPU (so101_tree_render).
 
@@ -443,17 +365,10 @@ class AlohaEnvironment(ToolControl, _contacts.ContactSensing, ProximitySensing, 
         (`meta["geom_names"][i]` names it), -1 where it hits nothing.  This is not RGB: textures and visual-only meshes are not
         rendered, and a camera's horizontal extent follows from square pixels."""
         from . import cameras as _cameras
-        torch = self.torch
         cams = [c.with_body_ids(self.meta["body_names"]) for c in _cameras.resolve(camera, _cameras.ALOHA_CAMERAS)]
         if delayed and not self._with_state:
             raise ValueError("render_depth(delayed=True) needs the physics-state delay line: create the environment with physics_state=True")
-        self._ensure_hull_planes()
-        idx, n = self._env_index(env_ids)
-        depth = torch.empty(n, len(cams), int(height), int(width), dtype=torch.float32, device=self.device)
-        seg = torch.empty(n, len(cams), int(height), int(width), dtype=torch.int32, device=self.device) if segmentation else None
-        self.sim.render([c.spec() for c in cams], height, width, idx.data_ptr() if idx is not None else None, n,
-                        depth.data_ptr(), seg.data_ptr() if seg is not None else None, self._stream(), source=1 if delayed else 0)
-        return depth, seg
+        return self._render_depth(cams, height, width, env_ids, segmentation, source=1 if delayed else 0)
 
     # ------------------------------------------------------------------ colour cameras (appearance.py: ColorCameras)
     _scene_shading = _appearance.ALOHA_SHADING
@@ -520,7 +435,7 @@ class AlohaEnvironment(ToolControl, _contacts.ContactSensing, ProximitySensing, 
     def _action_columns(self):
         """dof -> action column of the actuated arm joints (the grippers' entries are in follower units, not joint values: left out)"""
         if getattr(self, "_act_cols", None) is None:
-            m = blobfmt.unpack(self.task.load_blob("f32")[0])
+            m = self._model()
             grip = np.asarray(m["task_act_is_gripper"]).ravel()
             self._act_cols = {int(d): a for a, d in enumerate(np.asarray(m["act_dof"]).ravel()) if not int(grip[a])}
             self._grip_cols = [a for a in range(len(grip)) if int(grip[a])]
@@ -568,7 +483,7 @@ class AlohaEnvironment(ToolControl, _contacts.ContactSensing, ProximitySensing, 
 
     def _geom_groups(self):
         if getattr(self, "_groups", None) is None:
-            self._groups = _contacts.aloha_groups(self.meta, blobfmt.unpack(self.task.load_blob("f32")[0]))
+            self._groups = _contacts.aloha_groups(self.meta, self._model())
         return self._groups
 
     def geom_group(self, spec):
@@ -607,7 +522,7 @@ class AlohaEnvironment(ToolControl, _contacts.ContactSensing, ProximitySensing, 
         from . import tools as _tools
         if joints is None:
             if getattr(self, "_onedof_qadr", None) is None:
-                m = blobfmt.unpack(self.task.load_blob("f32")[0])
+                m = self._model()
                 jt, qadr = np.asarray(m["body_jnttype"]).ravel(), np.asarray(m["body_qposadr"]).ravel()
                 self._onedof_qadr = sorted(int(qadr[b]) for b in range(len(jt)) if int(jt[b]) in (native.TREE_JNT_HINGE, native.TREE_JNT_SLIDE))
             return list(self._onedof_qadr)
@@ -662,6 +577,3 @@ class AlohaEnvironment(ToolControl, _contacts.ContactSensing, ProximitySensing, 
         """per env: contacts, constraint rows, solver iterations, broadphase candidates, flags of the last substep"""
         self.sim.get_diag(self._diag.data_ptr(), self._stream())
         return self._diag
-
-    def close(self):
-        self.sim.close()

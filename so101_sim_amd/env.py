@@ -16,7 +16,6 @@ from __future__ import annotations
 
 import collections
 import hashlib
-import os
 
 import numpy as np
 
@@ -26,11 +25,8 @@ from .calibration import SO101Calibration
 from .model import scenes
 from . import appearance as _appearance
 from . import contacts as _contacts
-from . import proximity as _proximity
-from .tool_control import ToolControl
+from ._env_base import DEFAULT_CONTROL_TIMESTEP, PHYSICS_TIMESTEP, SETTLE_WARNING, EnvironmentBase, generator_of, pop_task_keywords
 
-DEFAULT_CONTROL_TIMESTEP = 0.02
-PHYSICS_TIMESTEP = 0.002
 _JOINT_DELAY_STEPS = 5       # 0.1 s / 0.02 s  (so100_task.py:81,196-201)
 _PHYSICS_DELAY_STEPS = 15    # 0.3 s / 0.02 s  (so100_task.py:80,204-210)
 
@@ -60,10 +56,7 @@ class SO100HandOverTask:
                 "contact+distance reward mode (so100_hand_over.py:277-318) is not built: in the reference that branch looks up "
                 "a body 'so100/hand_link' which scene_pbr.xml does not define, so it raises there as well")
         self.object_name = object_name
-        self.control_timestep = float(kwargs.pop("control_timestep", DEFAULT_CONTROL_TIMESTEP))
-        self.cameras = tuple(kwargs.pop("cameras", ()))
-        self.image_observation_enabled = bool(kwargs.pop("image_observation_enabled", True))
-        self.terminate_episode = bool(kwargs.pop("terminate_episode", True))
+        pop_task_keywords(self, kwargs)
         self.rotation_joint_limit = float(kwargs.pop("rotation_joint_limit", np.pi))
         self._instruction = scenes.HANDOVER_CONFIGS[object_name]["instruction"]
         # the calibration file is looked up relative to the CWD at construction time, as in the reference
@@ -120,43 +113,20 @@ class _PhysicsView:
         raise NotImplementedError("rendering is outside the MI355X hot path (SURVEY.md 8b)")
 
 
-class BatchedEnvironment(ToolControl, _contacts.ContactSensing, _proximity.ProximitySensing, _appearance.ColorCameras):
+class BatchedEnvironment(EnvironmentBase):
     def __init__(self, task: SO100HandOverTask, n_envs: int = 1, time_limit: float = float("inf"),
                  random_state=None, device=None, env_id_base: int = 0, solver_iterations: int = 0,
                  solver_tolerance: float = -1.0, settle_max_substeps: int = 1000, solver: str = "newton",
                  prefetch_resets: bool = True, physics_state: bool = False, narrowphase: str = "epa"):
-        import torch
-        if not torch.cuda.is_available():
-            raise RuntimeError("so101_sim_amd needs a ROCm GPU (MI355X): the step path has no CPU fallback")
-        self.torch = torch
-        self.task = task
-        self.n_envs = int(n_envs)
-        self.device = torch.device(device if device is not None else "cuda:0")
-        if isinstance(random_state, np.random.RandomState):
-            seed = int(random_state.randint(0, 2**31 - 1))
-        elif random_state is None:
-            seed = int.from_bytes(os.urandom(4), "little")
-        else:
-            seed = int(random_state)
-        self.seed = seed
-        blob, self.meta = scenes.load_blob(task.object_name, "f32")
-        dev_index = self.device.index or 0
+        self._open_device(task, n_envs, device, random_state)
+        torch, seed = self.torch, self.seed
+        blob, self.meta = self._load_blob("f32")
         with torch.cuda.device(self.device):
-            # narrowphase = "epa" (default): the penetration of non-flat convex pairs is the minimum translation (MPR's final portal
-            # expanded by EPA to the nearest face of the Minkowski difference, as mujoco >= 3.3's native GJK / EPA reports it - the
-            # reference pins mujoco>=3.3.3, requirements.txt:7).  "mpr": the -DSO101_MPR build of the library (built on demand) keeps
-            # MPR's portal depth: 5-15 % faster, 3x the physics errors under random actions (profiles/README.md)
-            if narrowphase not in ("mpr", "epa"):
-                raise ValueError(f"narrowphase must be 'mpr' or 'epa', got {narrowphase!r}")
-            from . import build as _build
-            self.narrowphase = narrowphase
-            # (SO101_HIP_LIB - kernel experiments, bench.py --pipeline 2|3 - names the library whatever the narrowphase: whoever sets it
-            #  built the variant it wants, e.g. build(exp=True, mpr=True); an explicit lib_path here used to override it)
-            import os as _os
-            lib = None if (_os.environ.get("SO101_HIP_LIB") or narrowphase != "mpr") else _build.build(mpr=True)
-            self.sim = native.Sim(blob, self.n_envs, device=dev_index, seed=seed, lib_path=lib)
+            # (an explicit lib_path here used to override SO101_HIP_LIB)
+            lib = self._narrowphase_library(narrowphase, env_names_library=True)
+            self.sim = native.Sim(blob, self.n_envs, device=self.device.index or 0, seed=seed, lib_path=lib)
         N = self.n_envs
-        z = lambda *s, dt=torch.float32: torch.zeros(*s, dtype=dt, device=self.device)
+        z = self._zeros
         self.qpos, self.qvel, self.ctrl, self.warm = z(20, N), z(18, N), z(6, N), z(18, N)
         self.ring, self.ep_return = z(native.RING_DEPTH, 6, N), z(N)
         self.step_count, self.episode = z(N, dt=torch.int32), z(N, dt=torch.int32)
@@ -182,11 +152,8 @@ class BatchedEnvironment(ToolControl, _contacts.ContactSensing, _proximity.Proxi
                                                  self.ep_return, self.step_count, self.episode, self.mass_scale)))
         # physics_state / delayed_physics_state (so100_task.py:203-210,366-368; the reference enables them together with the
         # cameras): device-side 15-step delay line, on request - the throughput configurations are proprioceptive only
-        self.physics_state = self.delayed_physics_state = self._ps_ring = None
         if physics_state:
-            self._ps_ring = z(native.PS_DELAY, native.PS_DIM, N)
-            self.physics_state, self.delayed_physics_state = z(N, native.PS_DIM), z(N, native.PS_DIM)
-            self.sim.bind_physics_state(self._ps_ring.data_ptr(), self.physics_state.data_ptr(), self.delayed_physics_state.data_ptr())
+            self._bind_physics_state(native.PS_DELAY, native.PS_DIM)
         nsub = int(round(task.control_timestep / PHYSICS_TIMESTEP))
         last = scenes.time_limit_last_step(time_limit, task.control_timestep, PHYSICS_TIMESTEP) if np.isfinite(time_limit) else 1 << 30
         self.last_step = last
@@ -223,10 +190,13 @@ class BatchedEnvironment(ToolControl, _contacts.ContactSensing, _proximity.Proxi
             spec["delayed_physics_state"] = Array((38,), np.float64, "delayed_physics_state")
         return spec
 
-    # ------------------------------------------------------------------ stepping (tensors in, tensors out)
-    def _stream(self):
-        return self.torch.cuda.current_stream(self.device).cuda_stream
+    def _load_blob(self, real: str):
+        return scenes.load_blob(self.task.object_name, real)
 
+    def _debug_layout(self):
+        return native.DBG, native.DEBUG_DIM
+
+    # ------------------------------------------------------------------ stepping (tensors in, tensors out)
     def reset_all(self):
         self.sim.reset(None, self._stream())
         N = self.n_envs
@@ -355,22 +325,6 @@ class BatchedEnvironment(ToolControl, _contacts.ContactSensing, _proximity.Proxi
         return header
 
     # ------------------------------------------------------------------ depth / segmentation cameras (cameras.py)
-    def _ensure_hull_planes(self):
-        """Facet planes of the mesh geoms' hulls, computed from the blob's vertices and handed to the library on first use"""
-        if getattr(self, "_planes_set", False):
-            return
-        from .model import blob as blobfmt, meshes
-        m = blobfmt.unpack(scenes.load_blob(self.task.object_name, "f32")[0])
-        verts = np.asarray(m["mesh_vert"], dtype=np.float64).reshape(-1, 3)
-        adr, chunks = [0], []
-        for t, a, n in zip(m["geom_type"], m["geom_vertadr"], m["geom_vertnum"]):
-            if int(t) == 5:
-                chunks.append(meshes.hull_planes(verts[a:a + n]))
-            adr.append(adr[-1] + (len(chunks[-1]) if int(t) == 5 else 0))
-        planes = np.concatenate(chunks) if chunks else np.zeros((0, 4))
-        self.sim.set_hull_planes(planes.astype(np.float32), np.asarray(adr, dtype=np.int32))
-        self._planes_set = True
-
     def render_depth(self, camera, height: int, width: int, env_ids=None, segmentation: bool = True):
         """Depth and geom-id images of the collision geometry at the current state, by ray casting on the GPU (so101_render).
 
@@ -380,15 +334,7 @@ class BatchedEnvironment(ToolControl, _contacts.ContactSensing, _proximity.Proxi
         distance along the optical axis, +inf where the ray hits nothing; seg the geom index (`meta["geom_names"][i]` names it),
         -1 where it hits nothing.  This is not RGB: textures and visual-only meshes are not rendered."""
         from . import cameras as _cameras
-        torch = self.torch
-        cams = _cameras.resolve(camera)
-        self._ensure_hull_planes()
-        idx, n = self._env_index(env_ids)
-        depth = torch.empty(n, len(cams), int(height), int(width), dtype=torch.float32, device=self.device)
-        seg = torch.empty(n, len(cams), int(height), int(width), dtype=torch.int32, device=self.device) if segmentation else None
-        self.sim.render([c.spec() for c in cams], height, width, idx.data_ptr() if idx is not None else None, n,
-                        depth.data_ptr(), seg.data_ptr() if seg is not None else None, self._stream())
-        return depth, seg
+        return self._render_depth(_cameras.resolve(camera), height, width, env_ids, segmentation)
 
     # ------------------------------------------------------------------ colour cameras (appearance.py: ColorCameras)
     _scene_shading = _appearance.SO100_SHADING
@@ -415,8 +361,7 @@ class BatchedEnvironment(ToolControl, _contacts.ContactSensing, _proximity.Proxi
     def _resolve_tool(self, tool):
         from . import tools as _tools
         if getattr(self, "_tools", None) is None:
-            from .model import blob as blobfmt
-            self._tools = _tools.so100_tools(self.meta, blobfmt.unpack(scenes.load_blob(self.task.object_name, "f32")[0]))
+            self._tools = _tools.so100_tools(self.meta, self._model())
         return _tools.resolve(tool, self._tools)
 
     def _tool_columns(self, t):
@@ -464,8 +409,7 @@ class BatchedEnvironment(ToolControl, _contacts.ContactSensing, _proximity.Proxi
 
     def _geom_groups(self):
         if getattr(self, "_groups", None) is None:
-            from .model import blob as blobfmt
-            self._groups = _contacts.so100_groups(self.meta, blobfmt.unpack(scenes.load_blob(self.task.object_name, "f32")[0]))
+            self._groups = _contacts.so100_groups(self.meta, self._model())
         return self._groups
 
     def geom_group(self, spec):
@@ -528,16 +472,6 @@ class BatchedEnvironment(ToolControl, _contacts.ContactSensing, _proximity.Proxi
         self.sim.get_diag(d.data_ptr(), self._stream())
         return d
 
-    def synchronize(self):
-        """Wait until everything this env was asked to do on the caller's current stream is done (steps, resets, reads).  Cheaper than
-        `torch.cuda.synchronize()` right after a mass reset: a device-wide synchronise also waits for the library's background reset
-        prefetch - settled initial states of FUTURE episodes, up to ~2 s of low-priority work on 256 wavefronts for 4096 envs - which no
-        result of the calls made so far depends on (bench.py reports both clocks, `sustained.host_env_steps_per_s` / `env_steps_per_s`)."""
-        self.torch.cuda.current_stream(self.device).synchronize()
-
-    def close(self):
-        self.sim.close()
-
 
 class SingleEnvironment(BatchedEnvironment):
     """N = 1 facade with the reference's numpy observation dict (keys/order:
@@ -553,25 +487,14 @@ class SingleEnvironment(BatchedEnvironment):
 
     def __init__(self, task, seed_compatible: bool = True, random_state=None, **kw):
         self._seed_compatible = bool(seed_compatible)
-        if isinstance(random_state, np.random.RandomState):
-            self._np_random = random_state
-        elif random_state is None:
-            self._np_random = np.random.RandomState()
-        else:
-            self._np_random = np.random.RandomState(int(random_state))
+        self._np_random = generator_of(random_state)
         if self._seed_compatible:
             kw.setdefault("prefetch_resets", False)      # the host draws the placements: nothing the kernels could settle ahead of time
         kw.pop("physics_state", None)                    # N = 1 keeps the reference's rule (image_observation_enabled) and a host-side line
         super().__init__(task, n_envs=1, random_state=(random_state if not isinstance(random_state, np.random.RandomState) else 0), **kw)
         self._state_ring = collections.deque(maxlen=_PHYSICS_DELAY_STEPS)
         self._pending_first = False
-        from .model import blob as blobfmt
-        m = blobfmt.unpack(scenes.load_blob(task.object_name, "f64")[0])
-        self._placer = dict(obj_lo=np.asarray(m["task_obj_pos_lo"], dtype=np.float64), obj_hi=np.asarray(m["task_obj_pos_hi"], dtype=np.float64),
-                            yaw=np.asarray(m["task_obj_yaw"], dtype=np.float64), con_lo=np.asarray(m["task_con_pos_lo"], dtype=np.float64),
-                            con_hi=np.asarray(m["task_con_pos_hi"], dtype=np.float64),
-                            con_geoms=set(np.nonzero(np.asarray(m["geom_body"]) == int(np.asarray(m["task_container_body"]).ravel()[0]))[0].tolist()))
-        self._dbg = self.torch.zeros(1, native.DEBUG_DIM, device=self.device)
+        self._placer = self._hand_over_placer()
         # a stream of its own: the library replays the step's launch chain as a captured HIP graph on any stream but the legacy null stream
         self._own = self.torch.cuda.Stream(device=self.device)
 
@@ -592,37 +515,9 @@ class SingleEnvironment(BatchedEnvironment):
         return self._host.numpy()
 
     # ---- reference-order placement + settle
-    def _container_collides(self) -> bool:
-        self.sim.debug_forward(self._dbg.data_ptr(), self._stream())
-        r = self._dbg[0].cpu().numpy()
-        D = native.DBG
-        ncon = int(r[D["COUNTS"]])
-        for k in range(ncon):
-            g1, g2 = int(r[D["CON"] + 10 * k + 7]), int(r[D["CON"] + 10 * k + 8])
-            if g1 in self._placer["con_geoms"] or g2 in self._placer["con_geoms"]:
-                return True
-        return False
-
     def _reset_seed_compatible(self):
-        torch, P, rs = self.torch, self._placer, self._np_random
-        opos = rs.uniform(P["obj_lo"], P["obj_hi"])                       # distributions.Uniform(low, high, single_sample=True)
-        yaw = rs.uniform(P["yaw"][0], P["yaw"][1])                        # QuaternionFromAxisAngle(axis=z, angle=Uniform)
-        q = np.zeros(20)
-        q[6:9] = opos
-        q[9:13] = [np.cos(0.5 * yaw), 0.0, 0.0, np.sin(0.5 * yaw)]
-        q[16] = 1.0
-        placed = False
-        for _ in range(20):                                               # PropPlacer max_attempts_per_prop
-            q[13:16] = rs.uniform(P["con_lo"], P["con_hi"])
-            self.qpos.copy_(torch.as_tensor(q, dtype=torch.float32, device=self.device).unsqueeze(1))
-            self.qvel.zero_()
-            self.warm.zero_()
-            if not self._container_collides():
-                placed = True
-                break
-        if not placed:
-            raise RuntimeError("Failed to place the container without collisions in 20 attempts (dm_control PropPlacer raises here too)")
-        self.placements = dict(object_position=opos.copy(), object_yaw=float(yaw), container_position=q[13:16].copy())
+        torch = self.torch
+        self._place_hand_over(np.zeros(20), 6, 13)
         before = self.events()["settle_not_converged"]          # (cumulative counters stay what events() documents)
         # settle with the controls the episode starts with (ctrl = home + offsets), like the kernels' own reset
         home = np.asarray(scenes.SO100_HOME_CTRL, dtype=np.float64)
@@ -632,7 +527,7 @@ class SingleEnvironment(BatchedEnvironment):
         self.begin_episode()
         if self.events()["settle_not_converged"] > before:
             import warnings
-            warnings.warn("Failed to settle physics within the settle budget (dm_control warns likewise)")
+            warnings.warn(SETTLE_WARNING)
 
     def _np_obs(self, first: bool, h=None):
         h = self._fetch() if h is None else h

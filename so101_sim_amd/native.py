@@ -28,17 +28,6 @@ MAXCON = 64
 DBG = dict(M=0, MINV=36, BIAS=72, SMOOTH=78, QACC=96, COUNTS=114, XPOS=120, CON=144, FORCE=144 + 10 * MAXCON,
            ROWF=144 + 16 * MAXCON, REWARD=144 + 16 * MAXCON + 16)
 
-EXPORTS = (
-    "so101_version", "so101_max_contacts", "so101_create", "so101_destroy", "so101_default_config",
-    "so101_configure", "so101_bind_state", "so101_bind_physics_state", "so101_set_reset_pool", "so101_compute_settled", "so101_set_settled_store", "so101_reset", "so101_settle", "so101_begin_episode", "so101_step", "so101_physics", "so101_reward",
-    "so101_get_returns", "so101_get_diag", "so101_get_events", "so101_debug_forward", "so101_debug_candidates", "so101_debug_stages", "so101_get_info", "so101_debug_chain_stats", "so101_last_error",
-    "so101_set_hull_planes", "so101_render", "so101_render_color", "so101_ik_default_config", "so101_tool_pose", "so101_tool_ik", "so101_contacts", "so101_proximity",
-    "so101_tree_create", "so101_tree_destroy", "so101_tree_dims", "so101_tree_last_plan", "so101_tree_bind_state", "so101_tree_configure", "so101_tree_physics",
-    "so101_tree_debug_forward", "so101_tree_get_diag", "so101_tree_last_error", "so101_tree_obs_dim", "so101_tree_bind_env",
-    "so101_tree_configure_env", "so101_tree_bind_physics_state", "so101_tree_reset", "so101_tree_step", "so101_tree_set_hull_planes", "so101_tree_render", "so101_tree_render_color", "so101_tree_begin_episode", "so101_tree_settle", "so101_tree_compute_settled", "so101_tree_set_settled_store",
-    "so101_tree_tool_chain", "so101_tree_ik_default_config", "so101_tree_tool_pose", "so101_tree_tool_ik", "so101_tree_contacts", "so101_tree_proximity",
-)
-
 
 class Buffers(C.Structure):
     _fields_ = [("qpos", C.c_void_p), ("qvel", C.c_void_p), ("ctrl", C.c_void_p), ("warmstart", C.c_void_p),
@@ -174,10 +163,103 @@ def tool_spec(tool) -> ToolSpec:
     return t
 
 
+class TreeConfig(C.Structure):
+    _fields_ = [("n_substeps", C.c_int), ("last_step", C.c_int), ("settle_max_substeps", C.c_int), ("terminate_on_success", C.c_int),
+                ("solver_iterations", C.c_int), ("solver_tolerance", C.c_float), ("seed", C.c_uint64), ("env_id_base", C.c_uint64),
+                ("reward_mode", C.c_int), ("reward_requires_handover", C.c_int),
+                ("joints_delay_steps", C.c_int), ("physics_delay_steps", C.c_int), ("prefetch_resets", C.c_int), ("pipeline", C.c_int)]
+
+
+TREE_DBG = dict(COUNTS=0, BIAS=8, QSM=40, QACC=72, XPOS=104, M=200, CON=1224, FORCE=1864, MSTRIDE=32)     # the 32-dof build; TreeSim.dbg is the handle's own
+
+# the struct(s) of include/so101.h each Structure mirrors (LightSpec: the unnamed element type of so101_shading.light)
+C_STRUCTS = {Buffers: ("so101_buffers",), Config: ("so101_config",), CameraSpec: ("so101_camera",), ShadingSpec: ("so101_shading",),
+             ColorOut: ("so101_color_out",), ToolSpec: ("so101_tool", "so101_tree_tool"), IkConfig: ("so101_ik_config",),
+             TreeIkConfig: ("so101_tree_ik_config",), GeomPair: ("so101_geom_pair",), TreeGeomPair: ("so101_tree_geom_pair",),
+             ContactOut: ("so101_contact_out",), ProximityOut: ("so101_proximity_out",), TreeConfig: ("so101_tree_config",)}
+
+
+def _signatures():
+    """export name -> (restype, argtypes): every prototype of include/so101.h, in its order (tests/test_abi_and_api.py compares the two)"""
+    i, f, vp, P = C.c_int, C.c_float, C.c_void_p, C.POINTER
+    cam, tool = P(CameraSpec), P(ToolSpec)
+    sig = {
+        "version": (i, []),
+        "max_contacts": (i, []),
+        "create": (i, [C.c_char_p, C.c_size_t, i, i, C.c_uint64, P(vp)]),
+        "destroy": (None, [vp]),
+        "default_config": (i, [P(Config)]),
+        "configure": (i, [vp, P(Config)]),
+        "bind_state": (i, [vp, P(Buffers)]),
+        "bind_physics_state": (i, [vp, vp, vp, vp]),
+        "reset": (i, [vp, vp, vp]),
+        "set_reset_pool": (i, [vp, vp, vp, vp, i]),
+        "compute_settled": (i, [vp, i, i, vp, vp, vp, vp, vp]),
+        "set_settled_store": (i, [vp, vp, vp, vp, vp, i, i]),
+        "settle": (i, [vp, vp]),
+        "begin_episode": (i, [vp, vp]),
+        "step": (i, [vp, vp, vp, vp, vp, vp, vp]),
+        "physics": (i, [vp, i, i, vp]),
+        "reward": (i, [vp, vp, vp]),
+        "get_returns": (i, [vp, vp, vp]),
+        "get_diag": (i, [vp, vp, vp]),
+        "get_events": (i, [vp, vp, i, vp]),
+        "debug_forward": (i, [vp, vp, vp]),
+        "debug_stages": (i, [vp, vp, vp]),
+        "debug_candidates": (i, [vp, vp, vp, vp, vp, vp]),
+        "get_info": (C.c_longlong, [vp, i, vp]),
+        "debug_chain_stats": (i, [vp, vp, i, vp]),
+        "set_hull_planes": (i, [vp, vp, vp]),
+        "render": (i, [vp, cam, i, i, i, vp, i, vp, vp, vp]),
+        "render_color": (i, [vp, cam, i, i, i, vp, i, P(ShadingSpec), vp, i, P(ColorOut), vp]),
+        "ik_default_config": (i, [vp, P(IkConfig)]),
+        "tool_pose": (i, [vp, tool, vp, vp, i, vp, vp, vp, vp]),
+        "tool_ik": (i, [vp, tool, P(IkConfig), vp, vp, vp, vp, i, vp, vp, vp, vp]),
+        "contacts": (i, [vp, vp, i, i, P(GeomPair), i, P(ContactOut), vp]),
+        "proximity": (i, [vp, vp, i, vp, P(GeomPair), i, f, P(ProximityOut), vp]),
+        "last_error": (C.c_char_p, [vp]),
+        "tree_create": (i, [C.c_char_p, C.c_size_t, i, i, P(vp)]),
+        "tree_destroy": (None, [vp]),
+        "tree_dims": (i, [vp, P(i)]),
+        "tree_last_plan": (i, [vp, P(i)]),
+        "tree_bind_state": (i, [vp, vp, vp, vp, vp]),
+        "tree_configure": (i, [vp, i, f]),
+        "tree_physics": (i, [vp, i, vp]),
+        "tree_debug_forward": (i, [vp, vp, vp]),
+        "tree_get_diag": (i, [vp, vp, vp]),
+        "tree_obs_dim": (i, [vp]),
+        "tree_bind_env": (i, [vp, vp, vp, vp, vp, vp]),
+        "tree_configure_env": (i, [vp, P(TreeConfig)]),
+        "tree_bind_physics_state": (i, [vp, vp, vp, vp]),
+        "tree_reset": (i, [vp, vp, vp]),
+        "tree_compute_settled": (i, [vp, i, i, vp, vp, vp, vp, vp]),
+        "tree_set_settled_store": (i, [vp, i, i, vp, vp, vp, vp]),
+        "tree_settle": (i, [vp, vp]),
+        "tree_begin_episode": (i, [vp, vp]),
+        "tree_step": (i, [vp, vp, vp, vp, vp, vp, vp]),
+        "tree_set_hull_planes": (i, [vp, vp, vp]),
+        "tree_render": (i, [vp, cam, i, i, i, vp, i, i, vp, vp, vp]),
+        "tree_render_color": (i, [vp, cam, i, i, i, vp, i, i, P(ShadingSpec), vp, i, P(ColorOut), vp]),
+        "tree_tool_chain": (i, [vp, i, vp, vp, vp]),
+        "tree_ik_default_config": (i, [vp, i, P(TreeIkConfig)]),
+        "tree_tool_pose": (i, [vp, tool, vp, vp, i, vp, vp, vp, vp]),
+        "tree_tool_ik": (i, [vp, tool, P(TreeIkConfig), vp, vp, vp, vp, i, vp, vp, vp, vp]),
+        "tree_contacts": (i, [vp, vp, i, i, P(TreeGeomPair), i, P(ContactOut), vp]),
+        "tree_proximity": (i, [vp, vp, i, vp, P(C.c_int32), i, P(TreeGeomPair), i, f, P(ProximityOut), vp]),
+        "tree_last_error": (C.c_char_p, [vp]),
+    }
+    return {"so101_" + k: v for k, v in sig.items()}
+
+
+SIGNATURES = _signatures()
+EXPORTS = tuple(SIGNATURES)
+
 _libs: dict[str, C.CDLL] = {}
 
 
 def load_library(path: str | None = None) -> C.CDLL:
+    """The library at `path` (default LIB_PATH) with SIGNATURES applied, once per path: the product, its -DSO101_MPR / experimental builds and
+    the emulated build alike"""
     path = path or LIB_PATH
     if path in _libs:
         return _libs[path]
@@ -192,66 +274,37 @@ def load_library(path: str | None = None) -> C.CDLL:
     except ImportError:
         pass
     L = C.CDLL(path)
-    vp = C.c_void_p
-    L.so101_version.restype = C.c_int
-    L.so101_max_contacts.restype = C.c_int
-    L.so101_create.restype = C.c_int
-    L.so101_create.argtypes = [C.c_char_p, C.c_size_t, C.c_int, C.c_int, C.c_uint64, C.POINTER(vp)]
-    L.so101_destroy.argtypes = [vp]
-    L.so101_default_config.argtypes = [C.POINTER(Config)]
-    L.so101_configure.argtypes = [vp, C.POINTER(Config)]
-    L.so101_bind_state.argtypes = [vp, C.POINTER(Buffers)]
-    L.so101_bind_physics_state.argtypes = [vp, vp, vp, vp]
-    L.so101_set_reset_pool.argtypes = [vp, vp, vp, vp, C.c_int]
-    L.so101_compute_settled.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]
-    L.so101_set_settled_store.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.c_int]
-    L.so101_reset.argtypes = [vp, vp, vp]
-    L.so101_begin_episode.argtypes = [vp, vp]
-    L.so101_settle.argtypes = [vp, vp]
-    L.so101_step.argtypes = [vp, vp, vp, vp, vp, vp, vp]
-    L.so101_physics.argtypes = [vp, C.c_int, C.c_int, vp]
-    L.so101_reward.argtypes = [vp, vp, vp]
-    L.so101_get_returns.argtypes = [vp, vp, vp]
-    L.so101_get_diag.argtypes = [vp, vp, vp]
-    L.so101_get_events.argtypes = [vp, vp, C.c_int, vp]
-    L.so101_debug_forward.argtypes = [vp, vp, vp]
-    L.so101_debug_candidates.argtypes = [vp, vp, vp, vp, vp, vp]
-    L.so101_debug_stages.argtypes = [vp, vp, vp]
-    L.so101_debug_chain_stats.argtypes = [vp, vp, C.c_int, vp]
-    L.so101_get_info.restype = C.c_longlong
-    L.so101_get_info.argtypes = [vp, C.c_int, vp]
-    L.so101_last_error.restype = C.c_char_p
-    L.so101_last_error.argtypes = [vp]
-    L.so101_set_hull_planes.argtypes = [vp, vp, vp]
-    L.so101_render.argtypes = [vp, C.POINTER(CameraSpec), C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp]
-    L.so101_render_color.argtypes = [vp, C.POINTER(CameraSpec), C.c_int, C.c_int, C.c_int, vp, C.c_int, C.POINTER(ShadingSpec), vp, C.c_int, C.POINTER(ColorOut), vp]
-    L.so101_ik_default_config.argtypes = [vp, C.POINTER(IkConfig)]
-    L.so101_tool_pose.argtypes = [vp, C.POINTER(ToolSpec), vp, vp, C.c_int, vp, vp, vp, vp]
-    L.so101_tool_ik.argtypes = [vp, C.POINTER(ToolSpec), C.POINTER(IkConfig), vp, vp, vp, vp, C.c_int, vp, vp, vp, vp]
-    L.so101_contacts.argtypes = [vp, vp, C.c_int, C.c_int, C.POINTER(GeomPair), C.c_int, C.POINTER(ContactOut), vp]
-    L.so101_proximity.argtypes = [vp, vp, C.c_int, vp, C.POINTER(GeomPair), C.c_int, C.c_float, C.POINTER(ProximityOut), vp]
+    for name, (restype, argtypes) in SIGNATURES.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _libs[path] = L
     return L
 
 
-class Sim:
-    """Thin handle wrapper. All array arguments are raw device addresses (ints)."""
+class _Handle:
+    """What Sim and TreeSim share: creation, close, the error check and the bodies of the calls the two engines have under both prefixes.
+    The engine's foreign functions are resolved once per handle, as `_c_<name>` for `<_PREFIX><name>`; what differs between the engines
+    beyond the prefix is a parameter (`_WORDS`, `source`, `q_adr`)."""
+    _PREFIX = "so101_"
+    _WORDS = 4            # 32-bit words of a geom mask: GeomPair / TreeGeomPair
 
-    def __init__(self, blob_f32: bytes, n_envs: int, device: int = 0, seed: int = 0, lib_path: str | None = None):
+    def _create(self, lib_path, blob_f32: bytes, n_envs: int, *args):
         self.L = load_library(lib_path)
+        tree = self._PREFIX == "so101_tree_"
+        for name in SIGNATURES:
+            if name.startswith("so101_tree_") == tree:
+                setattr(self, "_c_" + name[len(self._PREFIX):], getattr(self.L, name))
         self.n_envs = int(n_envs)
         h = C.c_void_p()
-        rc = self.L.so101_create(blob_f32, len(blob_f32), self.n_envs, int(device), int(seed), C.byref(h))
+        rc = self._c_create(blob_f32, len(blob_f32), self.n_envs, *args, C.byref(h))
         if rc != 0:
-            msg = self.L.so101_last_error(None)
-            raise RuntimeError(f"so101_create failed ({rc}): {msg.decode() if msg else '?'}")
+            msg = self._c_last_error(None)
+            raise RuntimeError(f"{self._PREFIX}create failed ({rc}): {msg.decode() if msg else '?'}")
         self.h = h
-        self.cfg = Config()
-        self.L.so101_default_config(C.byref(self.cfg))
 
     def close(self):
         if getattr(self, "h", None):
-            self.L.so101_destroy(self.h)
+            self._c_destroy(self.h)
             self.h = None
 
     def __del__(self):
@@ -261,9 +314,56 @@ class Sim:
             pass
 
     def _check(self, rc: int, what: str):
+        """what: the entry point's name without the prefix"""
         if rc != 0:
-            msg = self.L.so101_last_error(self.h)
-            raise RuntimeError(f"{what} failed ({rc}): {msg.decode() if msg else '?'}")
+            msg = self._c_last_error(self.h)
+            raise RuntimeError(f"{self._PREFIX}{what} failed ({rc}): {msg.decode() if msg else '?'}")
+
+    def bind_physics_state(self, ring, physics_state, delayed):
+        self._check(self._c_bind_physics_state(self.h, *(C.c_void_p(x) if x else None for x in (ring, physics_state, delayed))), "bind_physics_state")
+
+    def _set_hull_planes(self, planes, plane_adr):
+        import numpy as np
+        planes = np.ascontiguousarray(planes, dtype=np.float32).reshape(-1, 4)
+        plane_adr = np.ascontiguousarray(plane_adr, dtype=np.int32)
+        self._check(self._c_set_hull_planes(self.h, planes.ctypes.data, plane_adr.ctypes.data), "set_hull_planes")
+
+    def _render(self, cams, height, width, env_index, n_render, depth, seg, stream, source=None):
+        """source: None on the SO100 engine, whose call has no such argument"""
+        self._check(self._c_render(self.h, camera_array(cams), len(cams), int(height), int(width), env_index, int(n_render),
+                                   *(() if source is None else (int(source),)), depth, seg, stream), "render")
+
+    def _render_color(self, cams, height, width, env_index, n_render, shading, geom_rgb, rgb_per_env, rgb, normal, depth, seg, stream, source=None):
+        out = ColorOut(rgb, normal, depth, seg)
+        self._check(self._c_render_color(self.h, camera_array(cams), len(cams), int(height), int(width), env_index, int(n_render),
+                                         *(() if source is None else (int(source),)), C.byref(shading_struct(shading)), geom_rgb,
+                                         int(bool(rgb_per_env)), C.byref(out), stream), "render_color")
+
+    def _tool_pose(self, tool, q, env_index, n, pos, mat, jac, stream):
+        self._check(self._c_tool_pose(self.h, C.byref(tool_spec(tool)), q, env_index, int(n), pos, mat, jac, stream), "tool_pose")
+
+    def _tool_ik(self, tool, cfg, target_pos, target_mat, q_init, env_index, n, q_out, residual, info, stream):
+        self._check(self._c_tool_ik(self.h, C.byref(tool_spec(tool)), C.byref(cfg), target_pos, target_mat, q_init, env_index, int(n),
+                                    q_out, residual, info, stream), "tool_ik")
+
+    def _contacts(self, env_index, n, forces, pairs, out, stream):
+        arr = geom_pair_array(pairs, self._WORDS) if pairs else None
+        self._check(self._c_contacts(self.h, env_index, int(n), int(bool(forces)), arr, len(pairs) if pairs else 0, C.byref(out), stream), "contacts")
+
+    def _proximity(self, env_index, n, q, pairs, max_dist, out, stream, q_adr=()):
+        """q_adr: () on the SO100 engine; on the tree engine (int32 array of the qpos addresses of q's columns or None, their count)"""
+        arr = geom_pair_array(pairs, self._WORDS) if pairs else None
+        self._check(self._c_proximity(self.h, env_index, int(n), q, *q_adr, arr, len(pairs) if pairs else 0, float(max_dist), C.byref(out), stream),
+                    "proximity")
+
+
+class Sim(_Handle):
+    """Thin handle wrapper. All array arguments are raw device addresses (ints)."""
+
+    def __init__(self, blob_f32: bytes, n_envs: int, device: int = 0, seed: int = 0, lib_path: str | None = None):
+        self._create(lib_path, blob_f32, n_envs, int(device), int(seed))
+        self.cfg = Config()
+        self._c_default_config(C.byref(self.cfg))
 
     def configure(self, **kw):
         for k, v in kw.items():
@@ -274,16 +374,16 @@ class Sim:
                 if not hasattr(self.cfg, k):
                     raise AttributeError(k)
                 setattr(self.cfg, k, v)
-        self._check(self.L.so101_configure(self.h, C.byref(self.cfg)), "so101_configure")
+        self._check(self._c_configure(self.h, C.byref(self.cfg)), "configure")
 
     def info(self, stream=0) -> dict:
         """Facts about the handle (so101_get_info): which step path ran, graph replay, scheduler aborts, scratch size."""
-        return {k: int(self.L.so101_get_info(self.h, v, C.c_void_p(stream))) for k, v in INFO.items()}
+        return {k: int(self._c_get_info(self.h, v, C.c_void_p(stream))) for k, v in INFO.items()}
 
     def chain_stats(self, clear=True, stream=0) -> dict:
         """Time accounting of the chained step's persistent kernel (so101_debug_chain_stats), seconds summed over wavefronts."""
         buf = (C.c_uint64 * 16)()
-        self._check(self.L.so101_debug_chain_stats(self.h, C.cast(buf, C.c_void_p), int(clear), C.c_void_p(stream)), "so101_debug_chain_stats")
+        self._check(self._c_debug_chain_stats(self.h, C.cast(buf, C.c_void_p), int(clear), C.c_void_p(stream)), "debug_chain_stats")
         k = ("t_pop", "t_idle", "t_narrow", "t_solve", "n_narrow", "n_solve", "n_idle", "waves", "t_life",
              "t_narrow_load", "t_narrow_pairs", "t_narrow_finish", "t_solve_load_gather", "t_solve_compute", "t_solve_store_broad", "t_solve_publish")
         d = {n: int(buf[i]) for i, n in enumerate(k)}
@@ -295,85 +395,72 @@ class Sim:
 
     def bind(self, qpos, qvel, ctrl, warmstart, obs_ring, ep_return, step_count, episode, mass_scale=None):
         b = Buffers(qpos, qvel, ctrl, warmstart, obs_ring, ep_return, step_count, episode, mass_scale)
-        self._check(self.L.so101_bind_state(self.h, C.byref(b)), "so101_bind_state")
-
-    def bind_physics_state(self, ring, physics_state, delayed):
-        self._check(self.L.so101_bind_physics_state(self.h, *(C.c_void_p(x) if x else None for x in (ring, physics_state, delayed))),
-                    "so101_bind_physics_state")
+        self._check(self._c_bind_state(self.h, C.byref(b)), "bind_state")
 
     def set_reset_pool(self, qpos, qvel, ctrl, pool_size: int):
-        self._check(self.L.so101_set_reset_pool(self.h, qpos, qvel, ctrl, int(pool_size)), "so101_set_reset_pool")
+        self._check(self._c_set_reset_pool(self.h, qpos, qvel, ctrl, int(pool_size)), "set_reset_pool")
 
     def compute_settled(self, first_episode: int, n_episodes: int, qpos, qvel, warm, flags, stream=0):
-        self._check(self.L.so101_compute_settled(self.h, int(first_episode), int(n_episodes), qpos, qvel, warm, flags, stream),
-                    "so101_compute_settled")
+        self._check(self._c_compute_settled(self.h, int(first_episode), int(n_episodes), qpos, qvel, warm, flags, stream), "compute_settled")
 
     def set_settled_store(self, qpos, qvel, warm, flags, first_episode: int, n_episodes: int):
-        self._check(self.L.so101_set_settled_store(self.h, qpos, qvel, warm, flags, int(first_episode), int(n_episodes)),
-                    "so101_set_settled_store")
+        self._check(self._c_set_settled_store(self.h, qpos, qvel, warm, flags, int(first_episode), int(n_episodes)), "set_settled_store")
 
     def reset(self, mask=None, stream=0):
-        self._check(self.L.so101_reset(self.h, mask, stream), "so101_reset")
+        self._check(self._c_reset(self.h, mask, stream), "reset")
 
     def settle(self, stream=0):
-        self._check(self.L.so101_settle(self.h, stream), "so101_settle")
+        self._check(self._c_settle(self.h, stream), "settle")
 
     def begin_episode(self, stream=0):
-        self._check(self.L.so101_begin_episode(self.h, stream), "so101_begin_episode")
+        self._check(self._c_begin_episode(self.h, stream), "begin_episode")
 
     def step(self, action, obs, reward, discount, step_type, stream=0):
-        self._check(self.L.so101_step(self.h, action, obs, reward, discount, step_type, stream), "so101_step")
+        self._check(self._c_step(self.h, action, obs, reward, discount, step_type, stream), "step")
 
     def physics(self, n_substeps: int, freeze_arm: bool = False, stream=0):
-        self._check(self.L.so101_physics(self.h, int(n_substeps), int(freeze_arm), stream), "so101_physics")
+        self._check(self._c_physics(self.h, int(n_substeps), int(freeze_arm), stream), "physics")
 
     def reward(self, out, stream=0):
-        self._check(self.L.so101_reward(self.h, out, stream), "so101_reward")
+        self._check(self._c_reward(self.h, out, stream), "reward")
 
     def get_returns(self, out, stream=0):
-        self._check(self.L.so101_get_returns(self.h, out, stream), "so101_get_returns")
+        self._check(self._c_get_returns(self.h, out, stream), "get_returns")
 
     def get_diag(self, out, stream=0):
-        self._check(self.L.so101_get_diag(self.h, out, stream), "so101_get_diag")
+        self._check(self._c_get_diag(self.h, out, stream), "get_diag")
 
     def get_events(self, out, clear=False, stream=0):
-        self._check(self.L.so101_get_events(self.h, out, int(bool(clear)), stream), "so101_get_events")
+        self._check(self._c_get_events(self.h, out, int(bool(clear)), stream), "get_events")
 
     def debug_candidates(self, ncand=None, cand=None, ticks=None, conres=None, stream=0):
-        self._check(self.L.so101_debug_candidates(self.h, ncand, cand, ticks, conres, stream), "so101_debug_candidates")
+        self._check(self._c_debug_candidates(self.h, ncand, cand, ticks, conres, stream), "debug_candidates")
 
     def debug_stages(self, out, stream=0):
-        self._check(self.L.so101_debug_stages(self.h, out, stream), "so101_debug_stages")
+        self._check(self._c_debug_stages(self.h, out, stream), "debug_stages")
 
     def debug_forward(self, out, stream=0):
-        self._check(self.L.so101_debug_forward(self.h, out, stream), "so101_debug_forward")
+        self._check(self._c_debug_forward(self.h, out, stream), "debug_forward")
 
     def set_hull_planes(self, planes, plane_adr):
         """planes [n, 4] float32 and plane_adr [ngeom + 1] int32: HOST numpy arrays (so101_set_hull_planes copies them)"""
-        import numpy as np
-        planes = np.ascontiguousarray(planes, dtype=np.float32).reshape(-1, 4)
-        plane_adr = np.ascontiguousarray(plane_adr, dtype=np.int32)
-        self._check(self.L.so101_set_hull_planes(self.h, planes.ctypes.data, plane_adr.ctypes.data), "so101_set_hull_planes")
+        self._set_hull_planes(planes, plane_adr)
 
     def render(self, cams, height: int, width: int, env_index, n_render: int, depth, seg, stream=0):
         """cams: sequence of (body, pos[3], mat[9] row-major, fovy_deg); env_index / depth / seg: raw device addresses or None"""
-        arr = camera_array(cams)
-        self._check(self.L.so101_render(self.h, arr, len(cams), int(height), int(width), env_index, int(n_render), depth, seg, stream), "so101_render")
+        self._render(cams, height, width, env_index, n_render, depth, seg, stream)
 
     def render_color(self, cams, height: int, width: int, env_index, n_render: int, shading, geom_rgb, rgb_per_env: bool = False,
                      rgb=None, normal=None, depth=None, seg=None, stream=0):
         """so101_render_color.  cams as for render; shading: what shading_struct() takes; geom_rgb / env_index / rgb / normal / depth / seg: raw
         device addresses or None (geom_rgb [ngeom, 3] float32, or [n_envs, ngeom, 3] with rgb_per_env)"""
-        arr = camera_array(cams)
-        out = ColorOut(rgb, normal, depth, seg)
-        self._check(self.L.so101_render_color(self.h, arr, len(cams), int(height), int(width), env_index, int(n_render), C.byref(shading_struct(shading)), geom_rgb,
-                                              int(bool(rgb_per_env)), C.byref(out), stream), "so101_render_color")
+        self._render_color(cams, height, width, env_index, n_render, shading, geom_rgb, rgb_per_env, rgb, normal, depth, seg, stream)
 
     def ik_config(self, **kw) -> IkConfig:
         """so101_ik_default_config (mode 1, 60 iterations, 1e-4 m, 1e-3 rad, the model's joint ranges) with the given fields replaced;
         q_lo / q_hi take sequences of 6"""
         cfg = IkConfig()
-        self._check(self.L.so101_ik_default_config(self.h, C.byref(cfg)), "so101_ik_default_config")
+        self._check(self._c_ik_default_config(self.h, C.byref(cfg)), "ik_default_config")
         for k, v in kw.items():
             if k in ("q_lo", "q_hi"):
                 getattr(cfg, k)[:] = [float(x) for x in v]
@@ -385,195 +472,116 @@ class Sim:
 
     def tool_pose(self, tool, q, env_index, n: int, pos, mat, jac, stream=0):
         """tool: (body, pos[3], mat[9] row-major); q / env_index / pos / mat / jac: raw device addresses or None (so101_tool_pose)"""
-        self._check(self.L.so101_tool_pose(self.h, C.byref(tool_spec(tool)), q, env_index, int(n), pos, mat, jac, stream), "so101_tool_pose")
+        self._tool_pose(tool, q, env_index, n, pos, mat, jac, stream)
 
     def tool_ik(self, tool, cfg: IkConfig, target_pos, target_mat, q_init, env_index, n: int, q_out, residual, info, stream=0):
         """so101_tool_ik; cfg from ik_config(); the arrays are raw device addresses or None"""
-        self._check(self.L.so101_tool_ik(self.h, C.byref(tool_spec(tool)), C.byref(cfg), target_pos, target_mat, q_init, env_index, int(n),
-                                         q_out, residual, info, stream), "so101_tool_ik")
+        self._tool_ik(tool, cfg, target_pos, target_mat, q_init, env_index, n, q_out, residual, info, stream)
 
     def contacts(self, env_index, n: int, forces: bool, pairs, out: ContactOut, stream=0):
         """so101_contacts; pairs: sequence of (a words[4], b words[4]) geom masks; env_index and the fields of `out`: raw device addresses or None"""
-        arr = geom_pair_array(pairs) if pairs else None
-        self._check(self.L.so101_contacts(self.h, env_index, int(n), int(bool(forces)), arr, len(pairs) if pairs else 0, C.byref(out), stream), "so101_contacts")
+        self._contacts(env_index, n, forces, pairs, out, stream)
 
     def proximity(self, env_index, n: int, q, pairs, max_dist: float, out: ProximityOut, stream=0):
         """so101_proximity; pairs: sequence of (a words[4], b words[4]) geom masks; env_index, q and the fields of `out`: raw device addresses or None"""
-        arr = geom_pair_array(pairs) if pairs else None
-        self._check(self.L.so101_proximity(self.h, env_index, int(n), q, arr, len(pairs) if pairs else 0, float(max_dist), C.byref(out), stream), "so101_proximity")
+        self._proximity(env_index, n, q, pairs, max_dist, out, stream)
 
 
-class TreeConfig(C.Structure):
-    _fields_ = [("n_substeps", C.c_int), ("last_step", C.c_int), ("settle_max_substeps", C.c_int), ("terminate_on_success", C.c_int),
-                ("solver_iterations", C.c_int), ("solver_tolerance", C.c_float), ("seed", C.c_uint64), ("env_id_base", C.c_uint64),
-                ("reward_mode", C.c_int), ("reward_requires_handover", C.c_int),
-                ("joints_delay_steps", C.c_int), ("physics_delay_steps", C.c_int), ("prefetch_resets", C.c_int), ("pipeline", C.c_int)]
-
-
-TREE_DBG = dict(COUNTS=0, BIAS=8, QSM=40, QACC=72, XPOS=104, M=200, CON=1224, FORCE=1864, MSTRIDE=32)     # the 32-dof build; TreeSim.dbg is the handle's own
-
-
-class TreeSim:
+class TreeSim(_Handle):
     """Handle of the general-tree engine (include/so101.h, so101_tree_*): the ALOHA scenes.  Array arguments are raw device
     addresses (ints), state arrays are [dim][n_envs] float32."""
+    _PREFIX = "so101_tree_"
+    _WORDS = 8
 
     def __init__(self, blob_f32: bytes, n_envs: int, device: int = 0, lib_path: str | None = None):
-        self.L = load_library(lib_path)
-        L = self.L
-        L.so101_tree_create.argtypes = [C.c_char_p, C.c_size_t, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
-        L.so101_tree_destroy.argtypes = [C.c_void_p]
-        L.so101_tree_destroy.restype = None
-        L.so101_tree_dims.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
-        L.so101_tree_last_plan.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
-        L.so101_tree_bind_state.argtypes = [C.c_void_p] + [C.c_void_p] * 4
-        L.so101_tree_configure.argtypes = [C.c_void_p, C.c_int, C.c_float]
-        L.so101_tree_physics.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-        L.so101_tree_debug_forward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-        L.so101_tree_get_diag.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-        L.so101_tree_last_error.argtypes = [C.c_void_p]
-        L.so101_tree_last_error.restype = C.c_char_p
-        L.so101_tree_obs_dim.argtypes = [C.c_void_p]
-        L.so101_tree_bind_env.argtypes = [C.c_void_p] + [C.c_void_p] * 5
-        L.so101_tree_configure_env.argtypes = [C.c_void_p, C.POINTER(TreeConfig)]
-        L.so101_tree_reset.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-        L.so101_tree_step.argtypes = [C.c_void_p] + [C.c_void_p] * 6
-        L.so101_tree_begin_episode.argtypes = [C.c_void_p, C.c_void_p]
-        L.so101_tree_settle.argtypes = [C.c_void_p, C.c_void_p]
-        L.so101_tree_compute_settled.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5
-        L.so101_tree_set_settled_store.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4
-        L.so101_tree_set_hull_planes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-        L.so101_tree_render.argtypes = [C.c_void_p, C.POINTER(CameraSpec), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.so101_tree_render_color.argtypes = [C.c_void_p, C.POINTER(CameraSpec), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(ShadingSpec), C.c_void_p, C.c_int,
-                                              C.POINTER(ColorOut), C.c_void_p]
-        vp = C.c_void_p
-        L.so101_tree_tool_chain.argtypes = [vp, C.c_int, vp, vp, vp]
-        L.so101_tree_ik_default_config.argtypes = [vp, C.c_int, C.POINTER(TreeIkConfig)]
-        L.so101_tree_tool_pose.argtypes = [vp, C.POINTER(ToolSpec), vp, vp, C.c_int, vp, vp, vp, vp]
-        L.so101_tree_tool_ik.argtypes = [vp, C.POINTER(ToolSpec), C.POINTER(TreeIkConfig), vp, vp, vp, vp, C.c_int, vp, vp, vp, vp]
-        L.so101_tree_contacts.argtypes = [vp, vp, C.c_int, C.c_int, C.POINTER(TreeGeomPair), C.c_int, C.POINTER(ContactOut), vp]
-        L.so101_tree_proximity.argtypes = [vp, vp, C.c_int, vp, C.POINTER(C.c_int32), C.c_int, C.POINTER(TreeGeomPair), C.c_int, C.c_float, C.POINTER(ProximityOut), vp]
-        self.n_envs = int(n_envs)
-        h = C.c_void_p()
-        rc = L.so101_tree_create(blob_f32, len(blob_f32), self.n_envs, int(device), C.byref(h))
-        if rc != 0:
-            msg = L.so101_tree_last_error(None)
-            raise RuntimeError(f"so101_tree_create failed ({rc}): {msg.decode() if msg else '?'}")
-        self.h = h
+        self._create(lib_path, blob_f32, n_envs, int(device))
         d = (C.c_int * 16)()
-        self._check(L.so101_tree_dims(h, d), "so101_tree_dims")
+        self._check(self._c_dims(self.h, d), "dims")
         self.nq, self.nv, self.nu, self.nbody, self.ngeom, self.debug_dim, self.max_contacts = list(d)[:7]
         # layout of so101_tree_debug_forward's row for this handle's build (32 or 64 dofs) and the build itself
         self.dbg = dict(COUNTS=0, BIAS=d[7], QSM=d[8], QACC=d[9], XPOS=d[10], M=d[11], CON=d[12], FORCE=d[13], MSTRIDE=d[14])
         self.build = int(d[15])
-        self.obs_dim = int(L.so101_tree_obs_dim(h))
+        self.obs_dim = int(self._c_obs_dim(self.h))
         self.cfg = TreeConfig(n_substeps=10, last_step=1 << 30, settle_max_substeps=1000, terminate_on_success=1, solver_iterations=0,
                               solver_tolerance=-1.0, seed=0, env_id_base=0, reward_mode=0, reward_requires_handover=0,
                               joints_delay_steps=-1, physics_delay_steps=-1, prefetch_resets=0, pipeline=0)
 
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.so101_tree_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _check(self, rc: int, what: str):
-        if rc != 0:
-            msg = self.L.so101_tree_last_error(self.h)
-            raise RuntimeError(f"{what} failed ({rc}): {msg.decode() if msg else '?'}")
-
     def bind(self, qpos, qvel, ctrl, warm):
-        self._check(self.L.so101_tree_bind_state(self.h, qpos, qvel, ctrl, warm), "so101_tree_bind_state")
+        self._check(self._c_bind_state(self.h, qpos, qvel, ctrl, warm), "bind_state")
 
     def configure(self, solver_iterations: int = 0, solver_tolerance: float = -1.0):
-        self._check(self.L.so101_tree_configure(self.h, int(solver_iterations), float(solver_tolerance)), "so101_tree_configure")
+        self._check(self._c_configure(self.h, int(solver_iterations), float(solver_tolerance)), "configure")
 
     def physics(self, n_substeps: int, stream: int = 0):
-        self._check(self.L.so101_tree_physics(self.h, int(n_substeps), stream), "so101_tree_physics")
+        self._check(self._c_physics(self.h, int(n_substeps), stream), "physics")
 
     def debug_forward(self, out, stream: int = 0):
-        self._check(self.L.so101_tree_debug_forward(self.h, out, stream), "so101_tree_debug_forward")
+        self._check(self._c_debug_forward(self.h, out, stream), "debug_forward")
 
     def get_diag(self, out, stream: int = 0):
-        self._check(self.L.so101_tree_get_diag(self.h, out, stream), "so101_tree_get_diag")
+        self._check(self._c_get_diag(self.h, out, stream), "get_diag")
 
     def bind_env(self, ring_pos, ring_vel, ep_return, step_count, episode):
-        self._check(self.L.so101_tree_bind_env(self.h, ring_pos, ring_vel, ep_return, step_count, episode), "so101_tree_bind_env")
-
-    def bind_physics_state(self, ring, physics_state, delayed):
-        self.L.so101_tree_bind_physics_state.argtypes = [C.c_void_p] * 4
-        self._check(self.L.so101_tree_bind_physics_state(self.h, *(C.c_void_p(x) if x else None for x in (ring, physics_state, delayed))),
-                    "so101_tree_bind_physics_state")
+        self._check(self._c_bind_env(self.h, ring_pos, ring_vel, ep_return, step_count, episode), "bind_env")
 
     def configure_env(self, **kw):
         for k, v in kw.items():
             if not hasattr(self.cfg, k):
                 raise TypeError(f"unknown config field {k}")
             setattr(self.cfg, k, v)
-        self._check(self.L.so101_tree_configure_env(self.h, C.byref(self.cfg)), "so101_tree_configure_env")
+        self._check(self._c_configure_env(self.h, C.byref(self.cfg)), "configure_env")
 
     def reset(self, mask=None, stream: int = 0):
-        self._check(self.L.so101_tree_reset(self.h, mask, stream), "so101_tree_reset")
+        self._check(self._c_reset(self.h, mask, stream), "reset")
 
     def last_plan(self):
         """(env slices, kernel launches, memsets, path) of the last so101_tree_step as the library enqueued it; path 0 = no step yet"""
         d = (C.c_int * 4)()
-        self._check(self.L.so101_tree_last_plan(self.h, d), "so101_tree_last_plan")
+        self._check(self._c_last_plan(self.h, d), "last_plan")
         return tuple(d)
 
     def step(self, action, obs, reward, discount, step_type, stream: int = 0):
-        self._check(self.L.so101_tree_step(self.h, action, obs, reward, discount, step_type, stream), "so101_tree_step")
+        self._check(self._c_step(self.h, action, obs, reward, discount, step_type, stream), "step")
 
     def begin_episode(self, stream: int = 0):
-        self._check(self.L.so101_tree_begin_episode(self.h, stream), "so101_tree_begin_episode")
+        self._check(self._c_begin_episode(self.h, stream), "begin_episode")
 
     def settle(self, stream: int = 0):
-        self._check(self.L.so101_tree_settle(self.h, stream), "so101_tree_settle")
+        self._check(self._c_settle(self.h, stream), "settle")
 
     def compute_settled(self, first_episode, count, qpos, qvel, warm, flags, stream: int = 0):
-        self._check(self.L.so101_tree_compute_settled(self.h, int(first_episode), int(count), qpos, qvel, warm, flags, stream), "so101_tree_compute_settled")
+        self._check(self._c_compute_settled(self.h, int(first_episode), int(count), qpos, qvel, warm, flags, stream), "compute_settled")
 
     def set_settled_store(self, first_episode, count, qpos, qvel, warm, flags):
-        self._check(self.L.so101_tree_set_settled_store(self.h, int(first_episode), int(count), qpos, qvel, warm, flags), "so101_tree_set_settled_store")
+        self._check(self._c_set_settled_store(self.h, int(first_episode), int(count), qpos, qvel, warm, flags), "set_settled_store")
 
     def set_hull_planes(self, planes, plane_adr):
         """planes [n, 4] float32 and plane_adr [ngeom + 1] int32: HOST numpy arrays (so101_tree_set_hull_planes copies them)"""
-        import numpy as np
-        planes = np.ascontiguousarray(planes, dtype=np.float32).reshape(-1, 4)
-        plane_adr = np.ascontiguousarray(plane_adr, dtype=np.int32)
-        self._check(self.L.so101_tree_set_hull_planes(self.h, planes.ctypes.data, plane_adr.ctypes.data), "so101_tree_set_hull_planes")
+        self._set_hull_planes(planes, plane_adr)
 
     def render(self, cams, height: int, width: int, env_index, n_render: int, depth, seg, stream=0, source: int = 0):
         """cams: sequence of (body, pos[3], mat[9] row-major, fovy_deg), body a tree body id (-1 or 0: the world); env_index / depth / seg: raw
         device addresses or None; source 0: the bound qpos, 1: the delayed physics-state line (so101_tree_bind_physics_state)"""
-        arr = camera_array(cams)
-        self._check(self.L.so101_tree_render(self.h, arr, len(cams), int(height), int(width), env_index, int(n_render), int(source), depth, seg, stream), "so101_tree_render")
+        self._render(cams, height, width, env_index, n_render, depth, seg, stream, source=source)
 
     def render_color(self, cams, height: int, width: int, env_index, n_render: int, shading, geom_rgb, rgb_per_env: bool = False,
                      rgb=None, normal=None, depth=None, seg=None, stream=0, source: int = 0):
         """so101_tree_render_color: native.Sim.render_color on this engine; cams and source as for render"""
-        arr = camera_array(cams)
-        out = ColorOut(rgb, normal, depth, seg)
-        self._check(self.L.so101_tree_render_color(self.h, arr, len(cams), int(height), int(width), env_index, int(n_render), int(source), C.byref(shading_struct(shading)),
-                                                   geom_rgb, int(bool(rgb_per_env)), C.byref(out), stream), "so101_tree_render_color")
+        self._render_color(cams, height, width, env_index, n_render, shading, geom_rgb, rgb_per_env, rgb, normal, depth, seg, stream, source=source)
 
     def tool_chain(self, body: int):
         """The columns of a tool on body `body` (so101_tree_tool_chain): (dof indices, qpos addresses, joint types 1 hinge / 3 slide), root first"""
         dof, qadr, jt = ((C.c_int32 * TREE_TOOL_MAXCOL)() for _ in range(3))
-        n = self.L.so101_tree_tool_chain(self.h, int(body), dof, qadr, jt)
+        n = self._c_tool_chain(self.h, int(body), dof, qadr, jt)
         if n < 0:
-            self._check(n, "so101_tree_tool_chain")
+            self._check(n, "tool_chain")
         return list(dof[:n]), list(qadr[:n]), list(jt[:n])
 
     def ik_config(self, body: int, **kw) -> TreeIkConfig:
         """so101_tree_ik_default_config for a tool on `body` (mode 1, 60 iterations, 1e-4 m, 1e-3 rad, the chain's joint ranges, the hinge columns
         free) with the given fields replaced; q_lo / q_hi take one value per column of the chain"""
         cfg = TreeIkConfig()
-        self._check(self.L.so101_tree_ik_default_config(self.h, int(body), C.byref(cfg)), "so101_tree_ik_default_config")
+        self._check(self._c_ik_default_config(self.h, int(body), C.byref(cfg)), "ik_default_config")
         for k, v in kw.items():
             if k in ("q_lo", "q_hi"):
                 v = [float(x) for x in v]
@@ -588,23 +596,21 @@ class TreeSim:
 
     def tool_pose(self, tool, q, env_index, n: int, pos, mat, jac, stream=0):
         """tool: (body id, pos[3], mat[9] row-major); q / env_index / pos / mat / jac: raw device addresses or None (so101_tree_tool_pose)"""
-        self._check(self.L.so101_tree_tool_pose(self.h, C.byref(tool_spec(tool)), q, env_index, int(n), pos, mat, jac, stream), "so101_tree_tool_pose")
+        self._tool_pose(tool, q, env_index, n, pos, mat, jac, stream)
 
     def tool_ik(self, tool, cfg: TreeIkConfig, target_pos, target_mat, q_init, env_index, n: int, q_out, residual, info, stream=0):
         """so101_tree_tool_ik; cfg from ik_config(); the arrays are raw device addresses or None"""
-        self._check(self.L.so101_tree_tool_ik(self.h, C.byref(tool_spec(tool)), C.byref(cfg), target_pos, target_mat, q_init, env_index, int(n),
-                                              q_out, residual, info, stream), "so101_tree_tool_ik")
+        self._tool_ik(tool, cfg, target_pos, target_mat, q_init, env_index, n, q_out, residual, info, stream)
 
     def contacts(self, env_index, n: int, forces: bool, pairs, out: ContactOut, stream=0):
         """so101_tree_contacts; pairs: sequence of (a words[8], b words[8]) geom masks; env_index and the fields of `out`: raw device addresses or
         None.  The per-contact fields of `out` have max_contacts slots per entry."""
-        arr = geom_pair_array(pairs, 8) if pairs else None
-        self._check(self.L.so101_tree_contacts(self.h, env_index, int(n), int(bool(forces)), arr, len(pairs) if pairs else 0, C.byref(out), stream), "so101_tree_contacts")
+        self._contacts(env_index, n, forces, pairs, out, stream)
 
     def proximity(self, env_index, n: int, q, q_adr, pairs, max_dist: float, out: ProximityOut, stream=0):
         """so101_tree_proximity; pairs: sequence of (a words[8], b words[8]) geom masks; q_adr: the qpos addresses of q's columns (a sequence of
         ints, host side) or None; env_index, q [n][len(q_adr)] and the fields of `out`: raw device addresses or None"""
-        arr = geom_pair_array(pairs, 8) if pairs else None
         adr = (C.c_int32 * len(q_adr))(*[int(a) for a in q_adr]) if q_adr is not None and len(q_adr) else None
-        self._check(self.L.so101_tree_proximity(self.h, env_index, int(n), q, adr, len(q_adr) if q_adr is not None else 0, arr, len(pairs) if pairs else 0, float(max_dist),
-                                                C.byref(out), stream), "so101_tree_proximity")
+        self._proximity(env_index, n, q, pairs, max_dist, out, stream, q_adr=(adr, len(q_adr) if q_adr is not None else 0))
+
+

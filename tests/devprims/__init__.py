@@ -30,38 +30,60 @@ HL_GRID, HL_CELLS, HL_MAX, SBT_GRID, NCPP = 8, 384, 128, 5, 5
 GEOM_WORDS = 19
 
 
-def _flags(kind):
+CSRC = os.path.join(ROOT, "so101_sim_amd", "csrc")
+
+
+def cached_build(src: str, kind: str, defines=(), extra_inputs=(), program: bool = False) -> str:
+    """The one probe build: compiles `src` unless tests/devprims/build/ already holds the result for this compiler command and these inputs.
+
+    kind "gpu" / "emu": a shared library as described at the top of this file, its inputs `src` and every csrc/*.hpp (and, emulated, the two
+    headers of tests/hostemu).  kind "host": plain host C++ with csrc/ and include/ on the include path, its input `src` alone; with `program` an
+    executable with its own main instead of a shared library.  defines: "NAME=value" strings.  extra_inputs: further files the source reads.
+    For "gpu", torch is imported first: PyTorch bundles its own HIP runtime, which must be the first one the process loads
+    (so101_sim_amd/native.py load_library)."""
     if kind == "gpu":
+        try:
+            import torch  # noqa: F401
+        except ImportError:
+            pass
         from so101_sim_amd import build as sbuild
-        return [sbuild.HIPCC, *sbuild.FLAGS, "-shared"]
-    return [os.environ.get("CXX", "g++"), "-O1", "-std=c++17", "-fPIC", "-shared", "-pthread", "-I" + EMU,
-            "-include", os.path.join(EMU, "wave_emu.hpp"), "-Wno-unknown-pragmas", "-x", "c++"]
-
-
-def _inputs(kind):
-    files = [SRC] + sorted(glob.glob(os.path.join(ROOT, "so101_sim_amd", "csrc", "*.hpp")))
+        cmd = [sbuild.HIPCC, *sbuild.FLAGS, "-shared"]
+    elif kind == "emu":
+        cmd = [os.environ.get("CXX", "g++"), "-O1", "-std=c++17", "-fPIC", "-shared", "-pthread", "-I" + EMU,
+               "-include", os.path.join(EMU, "wave_emu.hpp"), "-Wno-unknown-pragmas", "-x", "c++"]
+    elif kind == "host":
+        cmd = [os.environ.get("CXX", "g++"), "-O1", "-std=c++17", "-Wall", "-I" + CSRC, "-I" + os.path.join(ROOT, "include")]
+        cmd += [] if program else ["-fPIC", "-shared"]
+    else:
+        raise ValueError(kind)
+    cmd = cmd[:1] + ["-D" + d for d in defines] + cmd[1:]
+    inputs = [src]
+    if kind != "host":
+        inputs += sorted(glob.glob(os.path.join(CSRC, "*.hpp")))
     if kind == "emu":
-        files += [os.path.join(EMU, "wave_emu.hpp"), os.path.join(EMU, "hip", "hip_runtime.h")]
-    return files
+        inputs += [os.path.join(EMU, "wave_emu.hpp"), os.path.join(EMU, "hip", "hip_runtime.h")]
+    inputs += list(extra_inputs)
+    h = hashlib.sha256(kind.encode())
+    for a in cmd:
+        h.update(os.path.basename(a).encode())
+    for f in inputs:
+        h.update(os.path.basename(f).encode())
+        with open(f, "rb") as fh:
+            h.update(fh.read())
+    stem = os.path.splitext(os.path.basename(src))[0]
+    out = os.path.join(OUT, f"{stem}_{kind}_{h.hexdigest()[:16]}" + ("" if program else ".so"))
+    if not os.path.exists(out):
+        os.makedirs(OUT, exist_ok=True)
+        tmp = f"{out}.{os.getpid()}.tmp"
+        subprocess.check_call(cmd + ["-o", tmp, src])
+        os.replace(tmp, out)
+    return out
 
 
 def build(kind: str) -> str:
     if kind not in ("gpu", "emu"):
         raise ValueError(kind)
-    h = hashlib.sha256(kind.encode())
-    for a in _flags(kind):
-        h.update(os.path.basename(a).encode())
-    for f in _inputs(kind):
-        h.update(os.path.basename(f).encode())
-        with open(f, "rb") as fh:
-            h.update(fh.read())
-    lib = os.path.join(OUT, f"libsupport_probe_{kind}_{h.hexdigest()[:16]}.so")
-    if not os.path.exists(lib):
-        os.makedirs(OUT, exist_ok=True)
-        tmp = f"{lib[:-3]}.{os.getpid()}.tmp.so"
-        subprocess.check_call(_flags(kind) + ["-o", tmp, SRC])
-        os.replace(tmp, lib)
-    return lib
+    return cached_build(SRC, kind)
 
 
 def _f32(a, cols):

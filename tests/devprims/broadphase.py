@@ -4,9 +4,7 @@ builds per kind: engine 0 (SO100, so101_device.hpp), 32 and 64 (the two builds o
 from __future__ import annotations
 
 import ctypes as C
-import hashlib
 import os
-import subprocess
 
 import numpy as np
 
@@ -21,22 +19,7 @@ SBT_DIM = 6 * SBT_GRID * SBT_GRID
 def build(kind: str, engine: int) -> str:
     if kind not in ("gpu", "emu") or engine not in ENGINES:
         raise ValueError((kind, engine))
-    flags = devprims._flags(kind)
-    flags = flags[:1] + [f"-DBP_ENGINE={engine}"] + flags[1:]
-    h = hashlib.sha256(kind.encode())
-    for a in flags:
-        h.update(os.path.basename(a).encode())
-    for f in [SRC] + devprims._inputs(kind)[1:] + [os.path.join(devprims.ROOT, "include", "so101.h")]:
-        h.update(os.path.basename(f).encode())
-        with open(f, "rb") as fh:
-            h.update(fh.read())
-    lib = os.path.join(devprims.OUT, f"libbroadphase_probe{engine}_{kind}_{h.hexdigest()[:16]}.so")
-    if not os.path.exists(lib):
-        os.makedirs(devprims.OUT, exist_ok=True)
-        tmp = f"{lib[:-3]}.{os.getpid()}.tmp.so"
-        subprocess.check_call(flags + ["-o", tmp, SRC])
-        os.replace(tmp, lib)
-    return lib
+    return devprims.cached_build(SRC, kind, defines=[f"BP_ENGINE={engine}"], extra_inputs=[os.path.join(devprims.ROOT, "include", "so101.h")])
 
 
 class Probe:
@@ -45,12 +28,6 @@ class Probe:
 
     def __init__(self, kind: str, engine: int, blob_f32: bytes, frames=None, sbt: bool = True):
         self.kind, self.engine = kind, engine
-        if kind == "gpu":
-            # PyTorch bundles its own HIP runtime, which must be the first one the process loads (so101_sim_amd/native.py load_library)
-            try:
-                import torch  # noqa: F401
-            except ImportError:
-                pass
         L = self.lib = C.CDLL(build(kind, engine))
         vp, i = C.c_void_p, C.c_int
         L.probe_error.restype = C.c_char_p

@@ -3,9 +3,7 @@ tests/devprims/__init__.py builds support_probe.hip (same flags, same cache dire
 from __future__ import annotations
 
 import ctypes as C
-import hashlib
 import os
-import subprocess
 
 import numpy as np
 
@@ -18,21 +16,7 @@ HL_ROW_MAX = 32          # so101_model.hpp: the longest list a row of 16 lanes h
 def build(kind: str) -> str:
     if kind not in ("gpu", "emu"):
         raise ValueError(kind)
-    flags = devprims._flags(kind)
-    h = hashlib.sha256(kind.encode())
-    for a in flags:
-        h.update(os.path.basename(a).encode())
-    for f in [SRC] + devprims._inputs(kind):
-        h.update(os.path.basename(f).encode())
-        with open(f, "rb") as fh:
-            h.update(fh.read())
-    lib = os.path.join(devprims.OUT, f"liblist_rows_probe_{kind}_{h.hexdigest()[:16]}.so")
-    if not os.path.exists(lib):
-        os.makedirs(devprims.OUT, exist_ok=True)
-        tmp = f"{lib[:-3]}.{os.getpid()}.tmp.so"
-        subprocess.check_call(flags + ["-o", tmp, SRC])
-        os.replace(tmp, lib)
-    return lib
+    return devprims.cached_build(SRC, kind, extra_inputs=[devprims.SRC])          # (the source includes support_probe.hip)
 
 
 class Probes(devprims.Probes):
@@ -40,12 +24,6 @@ class Probes(devprims.Probes):
 
     def __init__(self, kind: str):
         self.kind = kind
-        if kind == "gpu":
-            # PyTorch bundles its own HIP runtime, which must be the first one the process loads (so101_sim_amd/native.py load_library)
-            try:
-                import torch  # noqa: F401
-            except ImportError:
-                pass
         L = self.lib = C.CDLL(build(kind))
         vp, i = C.c_void_p, C.c_int
         L.probe_create.restype = vp

@@ -3,32 +3,18 @@ under tests/devprims/build/ by a hash of the compiler command and the two source
 from __future__ import annotations
 
 import ctypes as C
-import hashlib
 import os
-import subprocess
 
 from tests import devprims
 
 SRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "plan_probe.cpp")
-CSRC = os.path.join(devprims.ROOT, "so101_sim_amd", "csrc")
-HEADER = os.path.join(CSRC, "so101_step_plan.hpp")
+HEADER = os.path.join(devprims.CSRC, "so101_step_plan.hpp")
 KNOBS = ("narrow_chunk", "narrow_chunk_light", "narrow_rows", "narrow_list_rows", "narrow_waves_q", "tree_slices", "tree_narrow_waves_q")
 UNSET = dict(narrow_chunk=0, narrow_chunk_light=0, narrow_rows=-1, narrow_list_rows=-1, narrow_waves_q=0, tree_slices=0, tree_narrow_waves_q=0)
 
 
 def build() -> str:
-    cmd = [os.environ.get("CXX", "g++"), "-O1", "-std=c++17", "-fPIC", "-shared", "-Wall", "-I" + CSRC]
-    h = hashlib.sha256(" ".join(os.path.basename(a) for a in cmd).encode())
-    for f in (SRC, HEADER):
-        with open(f, "rb") as fh:
-            h.update(fh.read())
-    lib = os.path.join(devprims.OUT, f"libplan_probe_{h.hexdigest()[:16]}.so")
-    if not os.path.exists(lib):
-        os.makedirs(devprims.OUT, exist_ok=True)
-        tmp = f"{lib[:-3]}.{os.getpid()}.tmp.so"
-        subprocess.check_call(cmd + ["-o", tmp, SRC])
-        os.replace(tmp, lib)
-    return lib
+    return devprims.cached_build(SRC, "host", extra_inputs=[HEADER])
 
 
 class Probe:

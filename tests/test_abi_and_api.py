@@ -21,6 +21,145 @@ def test_library_exports_every_declared_symbol(hip_lib):
     assert lib.so101_version() == 10 and lib.so101_max_contacts() >= 16
 
 
+def _header_prototypes():
+    """[(return type, name, [parameter, ...])] of every so101_* prototype of include/so101.h, comments and preprocessor lines removed first
+    (prototypes carry comments with commas inside their parameter lists)"""
+    text = open(os.path.join(ROOT, "include", "so101.h")).read()
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", " ", text)
+    text = re.sub(r"^\s*#[^\n]*$", " ", text, flags=re.M)
+    out = []
+    for ret, name, params in re.findall(r"(?:^|[;{}])\s*([A-Za-z_][\w\s\*]*?)\s*\b(so101_\w+)\s*\(([^()]*)\)\s*(?=;)", text):
+        params = [" ".join(p.split()) for p in params.split(",")]
+        out.append((" ".join(ret.split()), name, [] if params == ["void"] else params))
+    return out
+
+
+def _ctype_class(t):
+    """(kind, bytes) of a ctypes type: compared by kind and size, not identity (c_size_t is c_uint64 here)"""
+    import ctypes as C
+    if t is None:
+        return ("void", 0)
+    if issubclass(t, C._Pointer) or t in (C.c_void_p, C.c_char_p):
+        return ("pointer", C.sizeof(t))
+    code = t._type_
+    kind = "float" if code in "fd" else "signed" if code in "bhilq" else "unsigned" if code in "BHILQ" else code
+    return (kind, C.sizeof(t))
+
+
+C_CLASSES = {"int": ("signed", 4), "int32_t": ("signed", 4), "size_t": ("unsigned", 8), "uint64_t": ("unsigned", 8), "float": ("float", 4)}
+C_RETURNS = {"int": "c_int", "void": None, "const char*": "c_char_p", "long long": "c_longlong"}
+
+
+def test_signature_table_matches_the_header():
+    """native.SIGNATURES against the prototypes of include/so101.h: the same 63 names, and per parameter and return value the same class
+    (pointer, 4-byte signed, 8-byte unsigned, float); a POINTER(Structure) only where the header names the struct that Structure mirrors,
+    and a struct pointer of the header never as a bare address."""
+    import ctypes as C
+    from so101_sim_amd import native
+    protos = _header_prototypes()
+    assert len(protos) == 63 and len({p[1] for p in protos}) == 63
+    assert {p[1] for p in protos} == set(native.SIGNATURES)
+    mirrored = {c: s for s, names in native.C_STRUCTS.items() for c in names}
+    for ret, name, params in protos:
+        restype, argtypes = native.SIGNATURES[name]
+        want = C_RETURNS[ret.replace(" *", "*")]
+        assert restype is (getattr(C, want) if want else None), (name, ret, restype)
+        assert len(argtypes) == len(params), (name, params, argtypes)
+        for k, (p, t) in enumerate(zip(params, argtypes)):
+            where = (name, k, p, t)
+            if "*" in p:
+                assert _ctype_class(t)[0] == "pointer", where
+                ctype = p.replace("const ", "").split("*")[0].strip()
+                if issubclass(t, C._Pointer) and issubclass(t._type_, C.Structure):
+                    assert ctype in native.C_STRUCTS[t._type_], where
+                elif ctype in mirrored:
+                    assert False, ("a struct pointer typed as a bare address", where)
+            else:
+                assert _ctype_class(t) == C_CLASSES[p.replace("const ", "").rsplit(" ", 1)[0]], where
+
+
+def _layout_fields(struct, prefix="", base=0):
+    """[(member path, offset, size)] of a ctypes Structure; arrays of structures are walked element by element"""
+    import ctypes as C
+    out = []
+    for fname, ftype in struct._fields_:
+        f = getattr(struct, fname)
+        if issubclass(ftype, C.Array) and issubclass(ftype._type_, C.Structure):
+            for k in range(ftype._length_):
+                out += _layout_fields(ftype._type_, f"{prefix}{fname}[{k}].", base + f.offset + k * C.sizeof(ftype._type_))
+        else:
+            out.append((prefix + fname, base + f.offset, f.size))
+    return out
+
+
+def test_struct_layouts_match_the_header():
+    """sizeof and every field's offset and size of the ctypes Structures against the structs of include/so101.h, as the host compiler lays them
+    out: a generated program prints them (LightSpec through the member paths of so101_shading.light[k])."""
+    import ctypes as C
+    import subprocess
+    from so101_sim_amd import native
+    from tests import devprims
+    assert set(native.C_STRUCTS) == {native.Buffers, native.Config, native.CameraSpec, native.ShadingSpec, native.ColorOut, native.ToolSpec, native.IkConfig,
+                                     native.TreeIkConfig, native.GeomPair, native.TreeGeomPair, native.ContactOut, native.ProximityOut, native.TreeConfig}
+    want, lines = {}, []
+    for struct, cnames in native.C_STRUCTS.items():
+        for c in cnames:
+            want[c] = (C.sizeof(struct), 0)
+            lines.append(f'  std::printf("{c} %zu 0\\n", sizeof({c}));')
+            for path, offset, size in _layout_fields(struct):
+                want[f"{c}.{path}"] = (offset, size)
+                lines.append(f'  std::printf("{c}.{path} %zu %zu\\n", offsetof({c}, {path}), sizeof((({c}*)0)->{path}));')
+    assert want["so101_shading.light[3].headlight"][1] == 4 and C.sizeof(native.LightSpec) * native.MAX_LIGHTS == native.ShadingSpec.light.size
+    text = '#include <cstddef>\n#include <cstdio>\n#include "so101.h"\nint main() {\n' + "\n".join(lines) + "\n  return 0;\n}\n"
+    os.makedirs(devprims.OUT, exist_ok=True)
+    src = os.path.join(devprims.OUT, "abi_layout.cpp")
+    tmp = f"{src}.{os.getpid()}.tmp"
+    with open(tmp, "w") as f:
+        f.write(text)
+    os.replace(tmp, src)
+    exe = devprims.cached_build(src, "host", extra_inputs=[os.path.join(ROOT, "include", "so101.h")], program=True)
+    got = {}
+    for line in subprocess.run([exe], capture_output=True, text=True, check=True).stdout.splitlines():
+        name, a, b = line.split()
+        got[name] = (int(a), int(b))
+    assert got == want, {k: (got.get(k), want.get(k)) for k in set(got) | set(want) if got.get(k) != want.get(k)}
+
+
+SURFACE_CLASSES = {"env": ("BatchedEnvironment", "SingleEnvironment", "SO100HandOverTask"),
+                   "aloha": ("AlohaEnvironment", "HandOverTask", "DiningPlaceInContainerTask"), "native": ("Sim", "TreeSim")}
+
+
+def python_surface() -> dict:
+    """{module.Class: {public callable or __init__: [str(inspect.signature), sha256 of inspect.getdoc]}} of the classes a caller sees
+    (scripts/make_golden_python_surface.py writes it to tests/golden/python_surface.json)"""
+    import hashlib
+    import importlib
+    import inspect
+    out = {}
+    for mod, classes in SURFACE_CLASSES.items():
+        m = importlib.import_module("so101_sim_amd." + mod)
+        for cname in classes:
+            cls = getattr(m, cname)
+            names = ["__init__"] + [n for n in dir(cls) if not n.startswith("_") and callable(getattr(cls, n))]
+            out[f"{mod}.{cname}"] = {n: [str(inspect.signature(getattr(cls, n))), hashlib.sha256((inspect.getdoc(getattr(cls, n)) or "").encode()).hexdigest()]
+                                     for n in names}
+    return out
+
+
+def test_python_surface_is_the_pinned_one():
+    """Names, signatures and docstrings of the public methods of the environment, task and handle classes are those of
+    tests/golden/python_surface.json (dumped from the commit before the host layer was unified)."""
+    import json
+    want = json.load(open(os.path.join(ROOT, "tests", "golden", "python_surface.json")))
+    got = python_surface()
+    assert set(got) == set(want)
+    # the one addition since the dump: synchronize() moved to the base of both environment classes, so AlohaEnvironment has it as well
+    assert got["aloha.AlohaEnvironment"].pop("synchronize") == want["env.BatchedEnvironment"]["synchronize"]
+    for cls in want:
+        assert got[cls] == want[cls], (cls, {n for n in set(got[cls]) | set(want[cls]) if got[cls].get(n) != want[cls].get(n)})
+
+
 def test_create_rejects_bad_blobs_without_gpu(hip_lib, blobs):
     from so101_sim_amd import native
     with pytest.raises(RuntimeError, match="bad blob magic"):
